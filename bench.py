@@ -12,10 +12,14 @@ one RCCL all-reduce per matvec) on the SAME problem => strong scaling.  `--chi 5
 fresh child processes, before anything here touches torch or the GPU) and relays rank 0's JSON line.
 `--backend cpu` runs the same driver on the CPU baseline library over gloo (launch-path rehearsal without GPUs).
 
-Prints ONE JSON line (rank 0).  `roofline` is for k_grouped_gemm_z (the H_eff apply launches inside the timed sweeps,
-HIP events recorded by the library on its launch stream); `cpu_baseline` times the CPU baseline library
-(oracle/cpu_backend: same C++ planner / sweep driver, OpenMP task-parallel host kernels, LAPACK zgesvd with one BLAS
-thread per task) on whole-sweep work of the same state, all host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, grows and warms up the state, times `--steps` sweeps and reports
+them (`value` = s per sweep, `ms_per_step`) with what the timed sweeps' own statistics give for free.  `--full` adds what
+the headline figure does not need: `roofline` is for k_grouped_gemm_z (the H_eff apply launches inside the timed sweeps,
+HIP events recorded by the library on its launch stream -- only switched on under --full); `cpu_baseline` times the CPU
+baseline library (oracle/cpu_backend: same C++ planner / sweep driver, OpenMP task-parallel host kernels, LAPACK zgesvd
+with one BLAS thread per task) on whole-sweep work of the same state, all host cores.
+`--dump-outputs DIR` writes what the last timed sweep computed (energies, Schmidt spectra, a seeded sample of the site
+tensors) as DIR/*.npy, float64; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -47,7 +51,7 @@ def parse():
     ap.add_argument("--grow-tol", type=float, default=1e-6)
     ap.add_argument("--profile", action="store_true", help="sync-bracketed per-stage host timers (perturbs timing)")
     ap.add_argument("--lanczos-tol", type=float, default=1e-10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=45.0,
                     help="seconds of CPU-baseline bond updates (sweep order from the same state); a sweep that does not fit is "
                          "extrapolated by the recorded per-bond work and the sample says so")
@@ -59,6 +63,11 @@ def parse():
     ap.add_argument("--backend", default="hip", choices=["hip", "cpu"],
                     help="cpu = rehearsal of the multi-rank launch path on the CPU baseline library over gloo (not a bench line)")
     ap.add_argument("--master-port", type=int, default=29533)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: HIP-event timing of the H_eff apply launches "
+                         "(`roofline`, incl. the offline traffic constant) and the CPU baseline library (`cpu_baseline`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed sweep computed as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
 
@@ -146,6 +155,83 @@ def cpu_baseline(eng_gpu, mpo_sites, opts, budget, log):
             "restatement": "CPU restatement of the path behind the same C ABI, not MPSKit (no Julia in the image)"}
 
 
+def roofline(stats, world, sweep_s, kd, args):
+    """--full: roofline of k_grouped_gemm_z over the H_eff applies of the timed sweeps (HIP events of the library) and the
+    sweep-level roofline of SURVEY 8(d)"""
+    L = args.L
+    # the library brackets every 8th matvec launch with HIP events on its launch stream and scales each solve's sample to
+    # the solve's launch count (an event marker costs ~5 us of pipeline bubble: timing every launch slowed the sweep by 3 %)
+    tstats = [s for s in stats if s.matvec_ms > 0.0]
+    k_ms = sum(s.matvec_ms for s in tstats)
+    k_n = sum(s.n_matvec for s in tstats)
+    k_fl = sum(s.n_matvec * s.apply_flops for s in tstats)
+    achieved = (k_fl / world) / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+    rf = {"bound": "mfma", "kernel": "k_grouped_gemm_z (H_eff apply)", "achieved": achieved,
+          "peak": PEAK_F64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_F64_MFMA_TFLOPS,
+          "traffic": None, "launches": k_n, "timed_sample": "every 8th launch (HIP events), scaled per solve", "avg_launch_us": (k_ms * 1e3 / k_n) if k_n else None,
+          "flop_per_launch": (k_fl / world / k_n) if k_n else None,
+          "share_of_sweep_time": (k_ms * 1e-3 / args.steps) / sweep_s if sweep_s > 0 else None}
+    # Sweep-level roofline as SURVEY 8(d) defines it: sum over the bond updates of the stage bounds, divided by the sweep
+    # time.  Per bond: H_eff applies n_matvec x max(F / peak_f64, B / peak_hbm); Lanczos vector algebra 16 |theta| (2 j + 4)
+    # bytes for iteration j of a restart cycle; SVD LAPACK-equivalent flops / peak_f64; environment update max(F / 2 /
+    # peak_f64, B / 2 / peak_hbm).  All counts come from the run's own per-bond statistics.
+    PEAK_F, PEAK_B = PEAK_F64_MFMA_TFLOPS * 1e12, 8.0e12
+    b_apply = b_lan = b_svd = b_env = 0.0
+    for s_ in stats:
+        one = max(s_.apply_flops / world / PEAK_F, s_.apply_bytes / PEAK_B)
+        b_apply += s_.n_matvec * one
+        b_lan += sum(16.0 * s_.theta_size * (2 * (j % kd) + 4) for j in range(s_.n_matvec)) / PEAK_B
+        b_svd += s_.svd_flops / PEAK_F
+        b_env += max(0.5 * s_.apply_flops / PEAK_F, 0.5 * s_.apply_bytes / PEAK_B)
+    bound = (b_apply + b_lan + b_svd + b_env) / args.steps
+    rf["sweep"] = {"frac": bound / sweep_s if sweep_s > 0 else None, "bound_s": bound,
+                   "stage_bound_s": {"apply": b_apply / args.steps, "lanczos_vectors": b_lan / args.steps,
+                                     "svd": b_svd / args.steps, "env": b_env / args.steps},
+                   "definition": "SURVEY 8(d): sum of per-stage roofline bounds (78.6 TFLOP/s f64, 8.0 TB/s HBM) / sweep time"}
+    # HBM traffic per launch comes from OFFLINE rocprofv3 PMC passes (counters cannot be read live); the number is a committed
+    # constant, not a measurement of this run: see profiles/pmc_traffic.json for how it was collected and corrected
+    try:
+        pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(f"L{L}_chi{args.chi}")
+        if pmc and world == 1 and args.model == "one_band":
+            rf["traffic"] = pmc["traffic_bytes_per_launch"]
+            rf["traffic_source"] = "offline PMC (FETCH_SIZE x2 + WRITE_SIZE, separate passes), profiles/pmc_traffic.json: " \
+                                   + str(pmc.get("source", "see file"))
+            rf["algorithmic_bytes_per_launch"] = sum(s.n_matvec * s.apply_bytes for s in stats) / max(k_n, 1)
+    except Exception:
+        pass
+    return rf
+
+
+MPS_SAMPLE, MPS_SAMPLE_SEED = 1 << 19, 20240607       # site-tensor entries kept by --dump-outputs (16 MB as 4 float64 each)
+
+
+def dump_outputs(eng, last, path):
+    """--dump-outputs DIR: what the last timed sweep handed its caller, as float64 .npy files.  The sweep's energy, the
+    per-bond energies and discarded weights, the bond dimensions, every bond's Schmidt values (sector table alongside),
+    and a fixed seeded sample of the MPS site tensors (per site: sub-blocks in sorted label order, row-major, flattened)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+    save("energy", [eng.energy])
+    save("bond_energies", [s.energy for s in last])
+    save("trunc_weights", [s.trunc_weight for s in last])
+    save("bond_dims", eng.bond_dims())
+    secs, vals = [], []
+    for b in range(1, eng.L):
+        for c, s in sorted(eng.spectrum(b).items()):
+            secs.append((b, c[0], c[1], len(s)))
+            vals.append(np.asarray(s, dtype=np.float64))
+    save("schmidt_sectors", np.array(secs, dtype=np.float64).reshape(-1, 4))          # bond, N, j, count
+    save("schmidt_values", np.concatenate(vals) if vals else np.zeros(0))
+    rows = []
+    for i in range(eng.L):
+        blocks = eng.download_site(i)
+        flat = np.concatenate([blocks[k].reshape(-1) for k in sorted(blocks)]) if blocks else np.zeros(0, np.complex128)
+        sel = np.unique(np.random.default_rng([MPS_SAMPLE_SEED, i]).integers(0, max(flat.size, 1), size=min(MPS_SAMPLE // eng.L, flat.size)))
+        rows.append(np.stack([np.full(sel.size, i), sel, flat[sel].real, flat[sel].imag], axis=1))
+    save("mps_sample", np.concatenate(rows))                                          # site, entry, re, im
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -176,7 +262,7 @@ def main():
             torch.cuda.set_device(local)
             dist.init_process_group("nccl", rank=rank, world_size=world)
         ops = HipOps(local)
-        ops.set_timing(True)
+        ops.set_timing(args.full)                     # HIP events around every 8th apply launch: only the roofline reads them
         if dist is not None:
             ops.set_comm(rank, world)                 # RCCL inside the library; the id travels through torch.distributed
         sync = torch.cuda.synchronize
@@ -244,15 +330,9 @@ def main():
         dt = float(tt.item())
     sweep_s = dt / args.steps
 
-    # ---- roofline of k_grouped_gemm_z over the H_eff applies of the timed sweeps (HIP events of the library) ----
     stats = list(eng.stats)
-    # the library brackets every 8th matvec launch with HIP events on its launch stream and scales each solve's sample to
-    # the solve's launch count (an event marker costs ~5 us of pipeline bubble: timing every launch slowed the sweep by 3 %)
-    tstats = [s for s in stats if s.matvec_ms > 0.0]
-    k_ms = sum(s.matvec_ms for s in tstats)
-    k_n = sum(s.n_matvec for s in tstats)
-    k_fl = sum(s.n_matvec * s.apply_flops for s in tstats)
-    achieved = (k_fl / world) / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, stats[-(2 * L - 3):], args.dump_outputs)
     bdims = eng.bonds
     out = {
         "metric": ("DMRG sweep time (s) + GS energy/site, 1-band Hubbard L=%d chi=%d" % (L, args.chi)) if args.model != "polyacetylene"
@@ -270,7 +350,7 @@ def main():
                    "parallelism": "sector-parallel apply x%d" % world, "backend": args.backend},
         "energy_per_site": E / L,
         "max_bond_dim": max(b.dim_full for b in bdims), "max_multiplets": max(b.multiplets for b in bdims),
-        "matvecs_per_sweep": k_n / args.steps,
+        "matvecs_per_sweep": sum(s.n_matvec for s in stats) / args.steps,
         "max_trunc_weight": max(s.trunc_weight for s in stats),
         "rank_cut": eng.rank_cut,
         "host_plan_s_per_sweep": sum(s.t_plan for s in stats) / args.steps,
@@ -284,47 +364,15 @@ def main():
         "svd": {"lapack_equiv_gflop_per_sweep": sum(s.svd_flops for s in stats) / args.steps / 1e9,
                 "achieved_tflops": sum(s.svd_flops for s in stats) / max(sum(s.t_svd for s in stats), 1e-9) / 1e12,
                 "max_jacobi_sweeps": max(s.jacobi_sweeps for s in stats)},
-        "roofline": {"bound": "mfma", "kernel": "k_grouped_gemm_z (H_eff apply)", "achieved": achieved,
-                     "peak": PEAK_F64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_F64_MFMA_TFLOPS,
-                     "traffic": None, "launches": k_n, "timed_sample": "every 8th launch (HIP events), scaled per solve", "avg_launch_us": (k_ms * 1e3 / k_n) if k_n else None,
-                     "flop_per_launch": (k_fl / world / k_n) if k_n else None,
-                     "share_of_sweep_time": (k_ms * 1e-3 / args.steps) / sweep_s if sweep_s > 0 else None},
     }
-    # Sweep-level roofline as SURVEY 8(d) defines it: sum over the bond updates of the stage bounds, divided by the sweep
-    # time.  Per bond: H_eff applies n_matvec x max(F / peak_f64, B / peak_hbm); Lanczos vector algebra 16 |theta| (2 j + 4)
-    # bytes for iteration j of a restart cycle; SVD LAPACK-equivalent flops / peak_f64; environment update max(F / 2 /
-    # peak_f64, B / 2 / peak_hbm).  All counts come from the run's own per-bond statistics.
-    PEAK_F, PEAK_B = PEAK_F64_MFMA_TFLOPS * 1e12, 8.0e12
-    kd = eng.krylovdim
-    b_apply = b_lan = b_svd = b_env = 0.0
-    for s_ in stats:
-        one = max(s_.apply_flops / world / PEAK_F, s_.apply_bytes / PEAK_B)
-        b_apply += s_.n_matvec * one
-        b_lan += sum(16.0 * s_.theta_size * (2 * (j % kd) + 4) for j in range(s_.n_matvec)) / PEAK_B
-        b_svd += s_.svd_flops / PEAK_F
-        b_env += max(0.5 * s_.apply_flops / PEAK_F, 0.5 * s_.apply_bytes / PEAK_B)
-    bound = (b_apply + b_lan + b_svd + b_env) / args.steps
-    out["roofline"]["sweep"] = {"frac": bound / sweep_s if sweep_s > 0 else None, "bound_s": bound,
-                                "stage_bound_s": {"apply": b_apply / args.steps, "lanczos_vectors": b_lan / args.steps,
-                                                  "svd": b_svd / args.steps, "env": b_env / args.steps},
-                                "definition": "SURVEY 8(d): sum of per-stage roofline bounds (78.6 TFLOP/s f64, 8.0 TB/s HBM) / sweep time"}
-    # HBM traffic per launch comes from OFFLINE rocprofv3 PMC passes (counters cannot be read live); the number is a committed
-    # constant, not a measurement of this run: see profiles/pmc_traffic.json for how it was collected and corrected
-    try:
-        pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(f"L{L}_chi{args.chi}")
-        if pmc and world == 1 and args.model == "one_band":
-            out["roofline"]["traffic"] = pmc["traffic_bytes_per_launch"]
-            out["roofline"]["traffic_source"] = "offline PMC (FETCH_SIZE x2 + WRITE_SIZE, separate passes), profiles/pmc_traffic.json: " \
-                                                + str(pmc.get("source", "see file"))
-            out["roofline"]["algorithmic_bytes_per_launch"] = sum(s.n_matvec * s.apply_bytes for s in stats) / max(k_n, 1)
-    except Exception:
-        pass
-    log(json.dumps(out))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "one_band" and args.backend == "hip":
-        try:
-            out["cpu_baseline"] = cpu_baseline(eng, mpo, {"chi": args.chi, "lanczos_tol": args.lanczos_tol}, args.cpu_budget, log)
-        except Exception as exc:     # the baseline is reporting only; never lose the GPU line
-            out["cpu_baseline"] = {"value": None, "unit": "s", "cores": 1, "kind": "port", "sample": f"failed: {exc!r}"}
+    if args.full:
+        out["roofline"] = roofline(stats, world, sweep_s, eng.krylovdim, args)
+        log(json.dumps(out))
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "one_band" and args.backend == "hip":
+            try:
+                out["cpu_baseline"] = cpu_baseline(eng, mpo, {"chi": args.chi, "lanczos_tol": args.lanczos_tol}, args.cpu_budget, log)
+            except Exception as exc:     # the baseline is reporting only; never lose the GPU line
+                out["cpu_baseline"] = {"value": None, "unit": "s", "cores": 1, "kind": "port", "sample": f"failed: {exc!r}"}
     out["total_runtime_s"] = time.perf_counter() - t_start
     if rank == 0:
         print(json.dumps(out), flush=True)

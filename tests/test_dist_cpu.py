@@ -119,7 +119,7 @@ def test_bench_launch_path_with_two_ranks_on_the_cpu_backend():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--backend", "cpu", "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--L", "8", "--chi", "32", "--grow", "16x1", "--master-port", "29617"], env=env, capture_output=True, text=True,
+                        "--L", "8", "--chi", "32", "--grow", "16x1", "--master-port", "29617", "--full"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
