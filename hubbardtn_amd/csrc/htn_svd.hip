@@ -1757,6 +1757,30 @@ __device__ __forceinline__ double ring_rotate(double2 (&a)[E], const double2 (&b
     return ratio2;
 }
 
+// Per-step split of a cross step (diagnostic build -DHTN_RING_PROF -DHTN_RING_STEP_PROF only, tools/ring_prof.py): shader-clock
+// stamps at the boundaries of LDS read | dot + sums | angle | update + write | barrier.  Each stamp drains the wave's LDS
+// operations (s_waitcnt lgkmcnt(0)), so a phase holds its own LDS latency, and the steps get slower (202 x 202: cross rotations
+// 222 instead of 180 us per sweep): the phase times of -DHTN_RING_PROF alone are the ones to compare.  Elsewhere the stamps
+// compile to nothing.
+struct RingStamps {
+    long long t[6];
+};
+#if defined(HTN_RING_STEP_PROF) && !defined(HTN_RING_PROF)
+#error "HTN_RING_STEP_PROF needs HTN_RING_PROF (the split is stored with the phase times)"
+#endif
+#ifdef HTN_RING_STEP_PROF
+#define RING_ST(st, i)                                                                                      \
+    do {                                                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"((st).t[i])::"memory");                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+    } while (0)
+#else
+#define RING_ST(st, i) \
+    do {               \
+    } while (0)
+#endif
+
 // The same rotation in SCALED ("fast") form for the cross rounds: a column is kept as (scale, stored vector) with true column =
 // scale * stored.  With the true g = sa sb g_st the update  [a' b'] = [a b] [[c, c q g], [-c q conj(g), c]]  becomes
 //   a_st' = a_st - (q sb^2 conj(g_st)) b_st,   b_st' = b_st + (q sa^2 g_st) a_st,   sa' = c sa,   sb' = c sb
@@ -1764,7 +1788,7 @@ __device__ __forceinline__ double ring_rotate(double2 (&a)[E], const double2 (&b
 // every round and are applied when the round ends (at most w factors c >= 1/sqrt 2 accumulate: no range issue).
 template <int GS, int E>
 __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const double2 (&b)[E], double2* b_out, double& aa, double& bb,
-                                                     double& sa, double& sb, double tol2, double zero2) {
+                                                     double& sa, double& sb, double tol2, double zero2, RingStamps& st) {
     // conj(a_st) * b_st in FOUR independent chains (even / odd elements x re / im): a dependent f64 multiply-add cannot issue
     // back to back, and with one busy wave per SIMD nothing else fills the slots
     double gr = 0.0, gi = 0.0, gr1 = 0.0, gi1 = 0.0;
@@ -1781,6 +1805,7 @@ __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const doub
     }
     gr = group_sum<GS>(gr + gr1);
     gi = group_sum<GS>(gi + gi1);
+    RING_ST(st, 2);
     if (aa <= zero2 || bb <= zero2) return 0.0;
     const double ss = sa * sb;
     const double g2 = ss * ss * fma(gr, gr, gi * gi);           // |g|^2 of the true columns
@@ -1801,24 +1826,45 @@ __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const doub
     const double nur = qa * gr, nui = qa * gi;                  // nu = q sa^2 g_st
     sa *= c;
     sb *= c;
+    RING_ST(st, 3);
+    // b' first (computed and handed to LDS), a' afterwards: the update of a (in registers, needed only by the next step's dot)
+    // covers the drain of the LDS writes that the barrier after the step waits for.  Interleaved per element, the last
+    // writes left the VALU with nothing to do; the arithmetic is the same.  Cross rotations per sweep: 202 x 202 189 -> 180 us,
+    // 400 x 400 486 -> 427 us (profiles/r04_ring_qr_phase_times.txt).
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         double2 nb;
         nb.x = fma(-nui, a[e].y, fma(nur, a[e].x, b[e].x));
         nb.y = fma(nui, a[e].x, fma(nur, a[e].y, b[e].y));
         b_out[GS * e] = nb;
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
         double x = fma(-mur, b[e].x, a[e].x), y = fma(-mur, b[e].y, a[e].y);
         a[e].x = fma(mui, b[e].y, x);
         a[e].y = fma(-mui, b[e].x, y);
     }
+    RING_ST(st, 4);
     return ratio2;
 }
 
 // all nt x nb cross pairs of the two resident panels: group g owns T column g in registers (and its tracked norm), B columns
 // pass through LDS, their tracked norms through bnorm[]
-template <int GS, int E>
+//   TWO = false (one partner per step, the default): in step s group g meets B column (g + s) mod wm; wm steps, one workgroup
+//     barrier each.
+//   TWO = true (two partners per step, GS = 16 only, HTN_RING_TWO_PARTNER=1): T columns 2i, 2i+1 sit in rows 2i, 2i+1 of ONE
+//     wave and meet the B pair (2j, 2j+1), j = (i + s) mod ceil(wm / 2), in two phases -- (2i, 2j) | (2i+1, 2j+1), then (2i, 2j+1) | (2i+1, 2j).  The
+//     B columns change rows between the phases through LDS inside the wave (the wave's LDS operations complete in order; the
+//     drain plus the compiler barrier keep the read after the write), so a workgroup barrier comes once per two meetings.
+//     The same rotations (ring_rotate_scaled) in another order inside the round; every cross pair still meets once per round.
+//     Odd or ragged panels: the missing column's row sits the phase out.  Measured no faster than TWO = false (202 x 202: the
+//     barrier is ~15 % of a step, the phase-2 read waits for the phase-1 writes, odd w wastes a phase per round) and one sweep
+//     more on some blocks of the headline: kept behind the switch.
+// split (diagnostic build): per-phase shader-clock sums of group 0 over the steps in which all its meetings rotated.
+template <int GS, int E, bool TWO>
 __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int nb, int tid, double tol2, double zero2, double* bnorm,
-                                             double* bscale) {
+                                             double* bscale, long long* split) {
+    static_assert(!TWO || GS == 16, "two partners per step need both rows of a pair in one wave");
     constexpr int mp = GS * E;
     const int grp = tid / GS, sub = tid % GS;
     const int wm = nt > nb ? nt : nb;
@@ -1850,23 +1896,62 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
         }
     }
     __syncthreads();
-    for (int s = 0; s < wm; ++s) {
-        int j = grp + s;
-        j = j >= wm ? j - wm : j;
-        if (own && j < nb) {
-            double2 b[E];
-            double2* bc = B + j * mp + sub;
+    constexpr int phases = TWO ? 2 : 1;
+    const int hp = TWO ? (wm + 1) >> 1 : wm;                   // steps per round
+    const int row = TWO ? (grp & 1) : 0, pr = TWO ? (grp >> 1) : grp;
+    (void)split;
+    for (int s = 0; s < hp; ++s) {
+        int jp = pr + s;
+        jp = jp >= hp ? jp - hp : jp;                           // (pr < hp for every group that owns a T column)
+#ifdef HTN_RING_STEP_PROF
+        long long acc[4] = {0, 0, 0, 0};
+        bool all = true;
+#endif
+        RingStamps st;
 #pragma unroll
-            for (int e = 0; e < E; ++e) b[e] = bc[GS * e];
-            double bb = bnorm[j], sb = bscale[j];
-            const double rr = ring_rotate_scaled<GS, E>(a, b, bc, aa, bb, sa, sb, tol2, zero2);
-            ratio = rr > ratio ? rr : ratio;
-            if (sub == 0) {
-                bnorm[j] = bb;
-                bscale[j] = sb;
+        for (int ph = 0; ph < phases; ++ph) {
+            const int j = TWO ? 2 * jp + (row ^ ph) : jp;
+            st.t[4] = 0;
+            RING_ST(st, 0);
+            if (own && j < nb) {
+                double2 b[E];
+                double2* bc = B + j * mp + sub;
+#pragma unroll
+                for (int e = 0; e < E; ++e) b[e] = bc[GS * e];
+                double bb = bnorm[j], sb = bscale[j];
+                RING_ST(st, 1);
+                const double rr = ring_rotate_scaled<GS, E>(a, b, bc, aa, bb, sa, sb, tol2, zero2, st);
+                ratio = rr > ratio ? rr : ratio;
+                if (sub == 0) {
+                    bnorm[j] = bb;
+                    bscale[j] = sb;
+                }
             }
+#ifdef HTN_RING_STEP_PROF
+            if (st.t[4] == 0) all = false;
+            else {
+                acc[0] += st.t[1] - st.t[0];
+                acc[1] += st.t[2] - st.t[1];
+                acc[2] += st.t[3] - st.t[2];
+                acc[3] += st.t[4] - st.t[3];
+            }
+#endif
+            // between the phases: the B column this row wrote is read by the other row of the wave
+            if (TWO && ph == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
+#ifdef HTN_RING_STEP_PROF
+        const long long tb = st.t[4];
+#endif
         __syncthreads();
+#ifdef HTN_RING_STEP_PROF
+        RING_ST(st, 5);
+        if (tid == 0 && all && tb != 0) {
+            for (int q = 0; q < 4; ++q) split[q] += acc[q];
+            split[4] += st.t[5] - tb;
+            split[5] += 1;
+            split[6] += phases;
+        }
+#endif
     }
     if (own) {                 // the scales come out with the columns: T from registers, B in place
 #pragma unroll
@@ -1922,10 +2007,10 @@ __device__ __forceinline__ double ring_intra(double2* T, int nt, double2* B, int
 }
 
 #ifdef HTN_RING_PROF        // diagnostic build only (tools/ring_prof.py): per-workgroup 100 MHz tick sums per phase
-__device__ long long g_ring_prof[256 * 8];
+__device__ long long g_ring_prof[256 * 16];
 extern "C" int htn_ring_prof_dump(long long* out) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ring_prof), sizeof(long long) * 256 * 8));
+    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ring_prof), sizeof(long long) * 256 * 16));
     return 0;
 }
 #define RING_T(var) const long long var = wall_clock64()
@@ -1948,6 +2033,7 @@ struct RingArgs {
     int arrive_off, fail_off, conv_off;      // in 32-bit words (conv_off even)
     int xcc_off;                 // 32-bit words: one per workgroup, XCD id + 1 once the workgroup has started
     int max_sweeps;
+    int two_partner;             // 1: two partner columns per cross step (HTN_RING_TWO_PARTNER=1, 16-lane form only)
     double tol;
     int* info;
     int* sweeps_out;             // host-mapped, [nl]: outer sweeps of each block (0 = failed)
@@ -2016,8 +2102,16 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     }
     __syncthreads();
 #ifdef HTN_RING_PROF
-    long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // cross | send+drain | flags+wait | recv | intra | conv | total | sweeps
+    // cross | send+drain | flags+wait | recv | intra | conv | total | sweeps,P | split of the cross steps (shader clock, see
+    // ring_cross): LDS read, dot + sums, angle, update + write, barrier, steps, meetings | shader clock over the run
+    long long prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const long long prof_t0 = wall_clock64();
+    long long prof_c0;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(prof_c0)::"memory");
+#endif
+    long long* split = nullptr;
+#ifdef HTN_RING_STEP_PROF
+    split = prof + 8;
 #endif
     int sweeps = 0;
     bool done = n < 2, ok = *s_ok != 0;
@@ -2029,7 +2123,13 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
             const int par = (int)(epoch & 1u);
             const int nt = ncols(s_top[k]), nb = ncols(s_bot[k]);
             RING_T(p0);
-            const double rr = ring_cross<GS, E>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16);
+            double rr;
+            if constexpr (GS == 16) {
+                if (A.two_partner) rr = ring_cross<GS, E, true>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16, split);
+                else rr = ring_cross<GS, E, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16, split);
+            } else {           // 64 lanes per column: the two rows of a pair would be two waves
+                rr = ring_cross<GS, E, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16, split);
+            }
             ratio = rr > ratio ? rr : ratio;
             RING_T(p1);
             RING_ACC(0, p0, p1);
@@ -2123,7 +2223,10 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     if (tid == 0 && blockIdx.x < 256) {
         prof[6] = wall_clock64() - prof_t0;
         prof[7] = (local ? 1000000 : 0) + sweeps * 1000 + P;
-        for (int q = 0; q < 8; ++q) g_ring_prof[blockIdx.x * 8 + q] = prof[q];
+        long long prof_c1;
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(prof_c1)::"memory");
+        prof[15] = prof_c1 - prof_c0;
+        for (int q = 0; q < 16; ++q) g_ring_prof[blockIdx.x * 16 + q] = prof[q];
     }
 #endif
     // ---- result: column norms -> S, columns (pivoting undone) -> G; the panels are wherever the tournament left them ----
@@ -2444,6 +2547,9 @@ extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_bloc
     // reads at run time, hands panels over through that L2.  Speed only: a block whose workgroups find themselves on
     // different XCDs uses the placement-independent hand-off.  HTN_RING_NO_XCD=1: dense placement, as before.
     static const bool no_xcd = htn_env_flag("HTN_RING_NO_XCD");
+    // HTN_RING_TWO_PARTNER=1: cross steps with two partner columns each (ring_cross; measured no faster);
+    // read at every call, so one process can run both forms
+    const bool ring_two_partner = htn_env_flag("HTN_RING_TWO_PARTNER");
     const int n_xcd = (!no_xcd && g_js.cu_count > 0 && g_js.cu_count % 8 == 0) ? 8 : 1;
     const int ring_cap = std::max(1, std::min(g_js.cu_count > 0 ? g_js.cu_count : 256, 256));
     // CU slots and panel width of every large block; batches of <= #CU workgroups (all workgroups of a launch must be
@@ -2608,6 +2714,7 @@ extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_bloc
         ra.perm = d_perm, ra.zero2 = d_zero, ra.mbox = (double2*)g_js.ring_mbox, ra.sync = (unsigned*)g_js.ring_sync;
         ra.arrive_off = arrive_off, ra.fail_off = fail_off, ra.conv_off = conv_off, ra.max_sweeps = max_sweeps, ra.tol = tol;
         ra.xcc_off = xcc_off;
+        ra.two_partner = ring_two_partner ? 1 : 0;
         ra.info = info_dev, ra.sweeps_out = d_ring_sw;
         for (auto& bt : ring_batches) {
             ra.items = (const RingItem*)g_js.ring_items + bt.first;

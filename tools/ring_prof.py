@@ -1,4 +1,5 @@
-"""diagnostic: per-phase time of k_jacobi_ring on one block (needs a library built with HTN_EXTRA_FLAGS=-DHTN_RING_PROF)"""
+"""diagnostic: per-phase time of k_jacobi_ring on one block (needs a library built with HTN_EXTRA_FLAGS=-DHTN_RING_PROF; with
+-DHTN_RING_STEP_PROF as well it also splits a cross step into its phases, at the price of slower steps)"""
 import ctypes as C
 import sys
 import numpy as np
@@ -28,9 +29,9 @@ for a in sys.argv[1:]:
         ops.lib.htn_qr_prof_dump(C.c_void_p(q.ctypes.data))
         print(f"{a}: k_qr_large us: window {q[0] / 100:.1f}  panel load {q[1] / 100:.1f}  panel steps {q[2] / 100:.1f}  flush {q[3] / 100:.1f}  "
               f"trailing {q[4] / 100:.1f}  total {q[5] / 100:.1f}  panels {q[6]}")
-    out = np.zeros(256 * 8, dtype=np.int64)
+    out = np.zeros(256 * 16, dtype=np.int64)
     ops.lib.htn_ring_prof_dump(C.c_void_p(out.ctypes.data))
-    out = out.reshape(256, 8)
+    out = out.reshape(256, 16)
     rows = [r for r in range(256) if out[r, 6] > 0]          # (grid positions with work: the XCD-aware placement leaves gaps)
     P = int(out[rows[0], 7] % 1000)
     sw = int(out[rows[0], 7] // 1000 % 1000)
@@ -39,3 +40,13 @@ for a in sys.argv[1:]:
     print(f"{a}: P={P} sweeps={sw} hand-off through one XCD's L2: {bool(local)}  grid positions {rows[:P]}  (us per sweep, per workgroup; 100 MHz ticks)")
     for k, r in enumerate(rows[:P]):
         print("  k=%2d " % k + "  ".join(f"{n} {out[r, q] / 100.0 / max(sw, 1):7.1f}" for q, n in enumerate(names)))
+    # split of the cross steps (wave 0, row 0; steps in which all its meetings rotated; shader clock converted through the
+    # run's total on both clocks)
+    split = ["LDS read", "dot+sums", "angle", "update+write", "barrier"]
+    tot = out[rows[:P], 8:13].sum(axis=0).astype(float)
+    steps, meets = int(out[rows[:P], 13].sum()), int(out[rows[:P], 14].sum())
+    us_per_tick = (out[rows[:P], 6].sum() / 100.0) / max(out[rows[:P], 15].sum(), 1)
+    if steps:
+        per = tot * us_per_tick / steps
+        print(f"  cross step split ({steps} steps, {meets / steps:.0f} meeting(s) per step, shader clock {1.0 / us_per_tick:.0f} MHz): "
+              + "  ".join(f"{n} {1000 * v:6.0f} ns" for n, v in zip(split, per)) + f"  step {1000 * per.sum():6.0f} ns")
