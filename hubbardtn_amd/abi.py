@@ -79,6 +79,21 @@ class SweepOpts(C.Structure):
                 ("profile", C.c_int32), ("pad", C.c_int32)]
 
 
+class IdmrgOpts(C.Structure):
+    """htn_idmrg_opts"""
+    _fields_ = [("sweep", SweepOpts), ("cell_sites", C.c_int32), ("window_dN", C.c_int32), ("tol", C.c_double),
+                ("min_steps", C.c_int32), ("maxiter", C.c_int32), ("sweeps_per_step", C.c_int32), ("warm_start", C.c_int32)]
+
+
+class IdmrgStats(C.Structure):
+    """htn_idmrg_stats"""
+    _fields_ = [("step", C.c_int32), ("sweeps", C.c_int32), ("converged", C.c_int32), ("finished", C.c_int32),
+                ("needs_window", C.c_int32), ("chi_full", C.c_int32), ("energy", C.c_double),
+                ("energy_per_site", C.c_double), ("delta", C.c_double)]
+
+
+assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(IdmrgStats) == 48
+
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
            "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z"]
@@ -88,7 +103,8 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_mps_destroy", "htn_bond_update", "htn_dmrg2_sweep", "htn_mps_theta_size", "htn_heff2_apply",
                   "htn_mps_get_theta", "htn_mps_nsites", "htn_mps_bond", "htn_mps_spectrum", "htn_mps_site_size",
                   "htn_mps_get_site", "htn_mps_env_size", "htn_mps_get_env", "htn_mps_env_blocks", "htn_mps_env_bond",
-                  "htn_plan_apply_dump", "htn_mps_cache_stats", "htn_balance_tiles"]
+                  "htn_plan_apply_dump", "htn_mps_cache_stats", "htn_balance_tiles",
+                  "htn_idmrg_create", "htn_idmrg_destroy", "htn_idmrg_boundary", "htn_idmrg_step", "htn_idmrg_window"]
 
 
 class GemmLaunch(C.Structure):
@@ -189,6 +205,12 @@ def declare_engine(lib):
                                         C.POINTER(i64)]
     lib.htn_mps_cache_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.htn_balance_tiles.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    lib.htn_idmrg_create.argtypes = [vp, vp, C.POINTER(IdmrgOpts), C.POINTER(vp)]
+    lib.htn_idmrg_destroy.argtypes = [vp]
+    lib.htn_idmrg_destroy.restype = None
+    lib.htn_idmrg_boundary.argtypes = [vp, i32, vp]
+    lib.htn_idmrg_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(IdmrgStats)]
+    lib.htn_idmrg_window.argtypes = [vp, C.POINTER(vp)]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

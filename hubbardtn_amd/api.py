@@ -64,6 +64,7 @@ class IDMRG2:
     krylovdim: int = 30
     eigsolve_tol: float = 1e-10
     sweeps_per_step: int = 6       # at most this many finite sweeps of the 2-cell window per growth step
+    driver: str = "python"         # growth loop: "python" (idmrg.idmrg2's loop) or "native" (htn_idmrg_* inside the library)
 
 
 @dataclass
@@ -170,7 +171,8 @@ def find_groundstate(psi: FiniteMPS, H, alg: DMRG2, envs=None):
         psi.result = _idmrg.idmrg2(psi.ops or _ops(), H.simul, chi_full=chi, cutoff=cut, tol=alg.tol,
                                    maxiter=alg.maxiter, sweeps_per_step=alg.sweeps_per_step,
                                    init_dimension=psi.max_dimension, krylovdim=alg.krylovdim,
-                                   lanczos_tol=alg.eigsolve_tol, seed=psi.seed, verbosity=alg.verbosity)
+                                   lanczos_tol=alg.eigsolve_tol, seed=psi.seed, verbosity=alg.verbosity,
+                                   driver=alg.driver)
         return psi, Environments(psi.result.engine), psi.result.delta
     eng = psi.engine
     if isinstance(alg.trscheme, truncdim):
@@ -194,10 +196,11 @@ def find_groundstate(psi: FiniteMPS, H, alg: DMRG2, envs=None):
 
 
 def compute_groundstate(simul: Simulation, L: int | None = None, tol: float = 1e-6, verbosity: int = 0,
-                        maxiter: int = 100, init_state=None, chi: int | None = None):
+                        maxiter: int = 100, init_state=None, chi: int | None = None, driver: str = "python"):
     """src:993-1030 restated for the finite chain: H = hamiltonian(simul); psi0 = initialize_mps(...);
     find_groundstate(psi0, H, DMRG2(trscheme = truncbelow(10^-svalue))) -- or truncdim(chi) when a
-    fixed bond dimension is requested (the configs of BASELINE.json)."""
+    fixed bond dimension is requested (the configs of BASELINE.json).  driver: growth loop of the infinite chain
+    (IDMRG2.driver)."""
     H = hamiltonian(simul, L)
     spin = bool(simul.kwargs.get("spin", False))
     psi0 = init_state if init_state is not None else initialize_mps(H, simul.P, simul.bond_dim, spin, simul.Q)
@@ -209,7 +212,7 @@ def compute_groundstate(simul: Simulation, L: int | None = None, tol: float = 1e
             # the fixed point of two-site updates with that Schmidt cut -- IDMRG2 -- once the cut is expressed for the doubled cell
             # this library uses (idmrg.schmidt_cut_scale: one sector family per bond instead of both at half weight)
             scheme = truncbelow(_idmrg.schmidt_cut_scale(simul) * 10.0 ** (-simul.svalue))
-        alg = IDMRG2(trscheme=scheme, tol=tol, verbosity=verbosity, maxiter=maxiter)
+        alg = IDMRG2(trscheme=scheme, tol=tol, verbosity=verbosity, maxiter=maxiter, driver=driver)
     else:
         alg = DMRG2(trscheme=scheme, tol=tol, verbosity=verbosity, maxiter=maxiter)
     psi, envs, delta = find_groundstate(psi0, H, alg)

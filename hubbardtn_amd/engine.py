@@ -100,6 +100,59 @@ class CMpo:
             self.lib.htn_mpo_destroy(h)
 
 
+def sweep_opts(chi_full=None, cutoff=0.0, krylovdim=30, lanczos_tol=1e-12, maxrestart=3, weighting="sqrtdim",
+               jacobi_tol=1e-14, jacobi_max_sweeps=40, svd_split=0, rank_cut=0.0, profile=False) -> abi.SweepOpts:
+    """htn_sweep_opts of the engine's keyword options"""
+    o = abi.SweepOpts()
+    o.chi_full = int(chi_full) if chi_full else 0
+    o.weighting = 0 if weighting == "sqrtdim" else 1
+    o.cutoff = float(cutoff)
+    o.krylovdim, o.maxrestart, o.lanczos_tol = int(krylovdim), int(maxrestart), float(lanczos_tol)
+    o.jacobi_tol, o.jacobi_max_sweeps = float(jacobi_tol), int(jacobi_max_sweeps)
+    o.svd_split_elems, o.rank_cut, o.profile = int(svd_split), float(rank_cut), 1 if profile else 0
+    return o
+
+
+class StateTables:
+    """an MPS as the ABI's tables (htn_mps_create / htn_idmrg_step): bond_ptr, sectors, sub_ptr, subs, data_ptr, data"""
+
+    def __init__(self, bond_ptr, sectors, sub_ptr, subs, data_ptr, data):
+        self.arrays = (bond_ptr, sectors, sub_ptr, subs, data_ptr, data)
+
+    def pointers(self):
+        return [a.ctypes.data for a in self.arrays]
+
+
+def state_tables(bonds, tensors) -> StateTables:
+    """bonds: list of {sector: count} for bonds 0..L; tensors: list of {(l, s, r): ndarray[n_l, n_r]}"""
+    bond_ptr, secs = [0], []
+    for b in bonds:
+        items = sorted((k, int(v)) for k, v in dict(b).items() if v > 0)
+        secs.extend((N, j, n) for (N, j), n in items)
+        bond_ptr.append(len(secs))
+    sec_arr = np.array(secs, dtype=np.int32).reshape(-1, 3).view(abi.SECTOR_DT).reshape(-1)
+    subs, sub_ptr, data_ptr, chunks, pos = [], [0], [0], [], 0
+    for t in tensors:
+        off = 0
+        for (l, s, r), blk in t.items():
+            blk = np.asarray(blk, dtype=np.complex128)
+            m, n = blk.shape
+            subs.append((l[0], l[1], s, r[0], r[1], m, off))
+            chunks.append(np.asfortranarray(blk).reshape(-1, order="F"))
+            off += m * n
+        sub_ptr.append(len(subs))
+        pos += off
+        data_ptr.append(pos)
+    sub_arr = np.array(subs, dtype=np.int64).reshape(-1, 7)
+    sb = np.zeros(max(len(subs), 1), dtype=abi.SUBBLOCK_DT)
+    if len(subs):
+        for k, f in enumerate(("lN", "lj", "s", "rN", "rj", "ld", "off")):
+            sb[f] = sub_arr[:, k]
+    data = np.concatenate(chunks) if chunks else np.zeros(1, dtype=np.complex128)
+    return StateTables(np.array(bond_ptr, dtype=np.int32), np.ascontiguousarray(sec_arr), np.array(sub_ptr, dtype=np.int32), sb,
+                       np.array(data_ptr, dtype=np.int64), data)
+
+
 class DMRG2:
     """finite two-site DMRG on reduced SU(2) x U(1) tensors -- handle of an `htn_mps` inside the library.
 
@@ -116,6 +169,30 @@ class DMRG2:
 
     def __init__(self, ops, mpo, bonds, tensors, chi_full=None, cutoff=0.0, krylovdim=30, lanczos_tol=1e-12,
                  maxrestart=3, weighting="sqrtdim", jacobi_tol=1e-14, jacobi_max_sweeps=40, left_env=None, right_env=None):
+        self._setup(ops, mpo, chi_full, cutoff, krylovdim, lanczos_tol, maxrestart, weighting, jacobi_tol, jacobi_max_sweeps)
+        tab = state_tables(bonds, tensors)
+        le = None if left_env is None else np.ascontiguousarray(left_env, dtype=np.complex128)
+        re_ = None if right_env is None else np.ascontiguousarray(right_env, dtype=np.complex128)
+        h = C.c_void_p()
+        abi.check(self.lib, self.lib.htn_mps_create(ops.ctx, self.cmpo.handle, self.L, *tab.pointers(),
+                                                    None if le is None else le.ctypes.data,
+                                                    None if re_ is None else re_.ctypes.data, C.byref(h)),
+                  "htn_mps_create")
+        self.handle = h
+
+    @classmethod
+    def wrap(cls, ops, mpo, handle, chi_full=None, cutoff=0.0, krylovdim=30, lanczos_tol=1e-12, maxrestart=3,
+             weighting="sqrtdim", jacobi_tol=1e-14, jacobi_max_sweeps=40):
+        """an engine around an existing `htn_mps` handle (e.g. the window of the native IDMRG2 driver, htn_idmrg_window).
+        The engine takes over that reference (released in __del__); mpo: the CMpo the handle was built on."""
+        self = cls.__new__(cls)
+        self._setup(ops, mpo, chi_full, cutoff, krylovdim, lanczos_tol, maxrestart, weighting, jacobi_tol, jacobi_max_sweeps)
+        if self.lib.htn_mps_nsites(handle) != self.L:
+            raise ValueError("DMRG2.wrap: the handle's chain length differs from the MPO's")
+        self.handle = handle
+        return self
+
+    def _setup(self, ops, mpo, chi_full, cutoff, krylovdim, lanczos_tol, maxrestart, weighting, jacobi_tol, jacobi_max_sweeps):
         self.ops, self.lib = ops, ops.lib
         self.cmpo = mpo if isinstance(mpo, CMpo) else CMpo(ops, mpo)
         self.mpo = self.cmpo.sites
@@ -129,43 +206,6 @@ class DMRG2:
         self.profile = False
         self.energy = None
         self.stats = []
-        L = self.L
-        bond_ptr, secs = [0], []
-        for b in bonds:
-            items = sorted((k, int(v)) for k, v in dict(b).items() if v > 0)
-            secs.extend((N, j, n) for (N, j), n in items)
-            bond_ptr.append(len(secs))
-        sec_arr = np.array(secs, dtype=np.int32).reshape(-1, 3).view(abi.SECTOR_DT).reshape(-1)
-        subs, sub_ptr, data_ptr, chunks, pos = [], [0], [0], [], 0
-        for i in range(L):
-            off = 0
-            for (l, s, r), blk in tensors[i].items():
-                blk = np.asarray(blk, dtype=np.complex128)
-                m, n = blk.shape
-                subs.append((l[0], l[1], s, r[0], r[1], m, off))
-                chunks.append(np.asfortranarray(blk).reshape(-1, order="F"))
-                off += m * n
-            sub_ptr.append(len(subs))
-            pos += off
-            data_ptr.append(pos)
-        sub_arr = np.array(subs, dtype=np.int64).reshape(-1, 7)
-        sb = np.zeros(max(len(subs), 1), dtype=abi.SUBBLOCK_DT)
-        if len(subs):
-            for k, f in enumerate(("lN", "lj", "s", "rN", "rj", "ld", "off")):
-                sb[f] = sub_arr[:, k]
-        data = np.concatenate(chunks) if chunks else np.zeros(1, dtype=np.complex128)
-        bp = np.array(bond_ptr, dtype=np.int32)
-        sp = np.array(sub_ptr, dtype=np.int32)
-        dp = np.array(data_ptr, dtype=np.int64)
-        le = None if left_env is None else np.ascontiguousarray(left_env, dtype=np.complex128)
-        re_ = None if right_env is None else np.ascontiguousarray(right_env, dtype=np.complex128)
-        h = C.c_void_p()
-        abi.check(self.lib, self.lib.htn_mps_create(ops.ctx, self.cmpo.handle, L, bp.ctypes.data, sec_arr.ctypes.data,
-                                                    sp.ctypes.data, sb.ctypes.data, dp.ctypes.data, data.ctypes.data,
-                                                    None if le is None else le.ctypes.data,
-                                                    None if re_ is None else re_.ctypes.data, C.byref(h)),
-                  "htn_mps_create")
-        self.handle = h
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -183,14 +223,9 @@ class DMRG2:
 
     # ---- options ----------------------------------------------------------------------------------
     def _opts(self, cutoff=None):
-        o = abi.SweepOpts()
-        o.chi_full = int(self.chi_full) if self.chi_full else 0
-        o.weighting = 0 if self.weighting == "sqrtdim" else 1
-        o.cutoff = float(self.cutoff if cutoff is None else cutoff)
-        o.krylovdim, o.maxrestart, o.lanczos_tol = int(self.krylovdim), int(self.maxrestart), float(self.lanczos_tol)
-        o.jacobi_tol, o.jacobi_max_sweeps = float(self.jacobi_tol), int(self.jacobi_max_sweeps)
-        o.svd_split_elems, o.rank_cut, o.profile = int(self.svd_split), float(self.rank_cut), 1 if self.profile else 0
-        return o
+        return sweep_opts(self.chi_full, self.cutoff if cutoff is None else cutoff, self.krylovdim, self.lanczos_tol,
+                          self.maxrestart, self.weighting, self.jacobi_tol, self.jacobi_max_sweeps, self.svd_split,
+                          self.rank_cut, self.profile)
 
     # ---- state queries ----------------------------------------------------------------------------
     @property

@@ -20,10 +20,12 @@ k = N Q - P sites (src:251) is this relabelling done once and for all.
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import abi
 from . import engine as _engine
 from . import models, mps
 
@@ -93,14 +95,18 @@ class IDMRGResult:
 
 
 def idmrg2(ops, sim, chi_full=None, cutoff=0.0, tol=1e-6, maxiter=100, sweeps_per_step=6, init_dimension=8,
-           krylovdim=30, lanczos_tol=1e-10, seed=1234, verbosity=0, min_steps=3, warm_start=None):
+           krylovdim=30, lanczos_tol=1e-10, seed=1234, verbosity=0, min_steps=3, warm_start=None, driver="python"):
     """-> IDMRGResult.  `sim` is an OB_Sim / MB_Sim (filling P/Q); truncation by truncdim(chi_full) and/or
     truncbelow(cutoff) exactly as in the finite engine.  warm_start: every window after the second starts from McCulloch's
     prediction built out of the previous window's halves (`_absorb`) instead of a random state.  Default: on for the
     SU(2)-symmetric modes; off for the spinful U(1) x U(1) mode, whose growth under a crude Schmidt cut has several
     self-consistent fixed points (symmetry-broken windows whose multiplets the cut has split) -- random restarts wander
     between them and find lower ones than a prediction that hands one of them on (two-band test/Spin.jl case: -0.61 against
-    -0.55)."""
+    -0.55).
+    driver: "python" runs the growth loop below over the finite engine; "native" runs the same rules inside the library
+    (htn_idmrg_*: boundary environments and window tensors stay on the device between steps, `_native_idmrg2`)."""
+    if driver not in ("python", "native"):
+        raise ValueError(f"idmrg2: driver must be 'python' or 'native', not {driver!r}")
     P, Q = int(sim.P), int(sim.Q)
     B = int(sim.bands)
     sym = models.symmetry_of(sim)
@@ -118,6 +124,9 @@ def idmrg2(ops, sim, chi_full=None, cutoff=0.0, tol=1e-6, maxiter=100, sweeps_pe
     key = lambda w: (tuple(w.left), tuple(w.right), tuple(w.entries))
     assert key(big[m0]) == key(big[m0 + T]) == key(big[m0 + W]), "MPO is not periodic with the unit cell"
     cmpo = _engine.CMpo(ops, models.MPO(sites, sym))
+    if driver == "native":
+        return _native_idmrg2(ops, cmpo, sym, T, dNw, chi_full, cutoff, tol, maxiter, sweeps_per_step, init_dimension,
+                              krylovdim, lanczos_tol, seed, verbosity, min_steps, warm_start)
     # step 0: the window alone.  Its MPO bonds are the bulk's (full width), so "open ends" are explicit boundary
     # environments: an empty chain to the left (only the implicit identity level is non-zero) and to the right
     bL = {(0, 0): 1}
@@ -188,6 +197,67 @@ def idmrg2(ops, sim, chi_full=None, cutoff=0.0, tol=1e-6, maxiter=100, sweeps_pe
     return IDMRGResult(energy_per_site=e_site, delta=delta, iterations=len(history), unit_cell=T,
                        bond_dims=eng.bond_dims(), spectrum=spec_prev, history=history, engine=eng, boundary=boundary,
                        sweeps=n_sweeps)
+
+
+def _native_idmrg2(ops, cmpo, sym, T, dNw, chi_full, cutoff, tol, maxiter, sweeps_per_step, init_dimension, krylovdim,
+                   lanczos_tol, seed, verbosity, min_steps, warm_start):
+    """idmrg2's loop driven through the library's step-wise driver (htn_idmrg_*): the host only supplies the random
+    windows the driver asks for (same seeds as the Python loop: seed + step) and reads the scalars of every step"""
+    lib = ops.lib
+    W = 2 * T
+    kw = dict(chi_full=chi_full, cutoff=cutoff, krylovdim=krylovdim, lanczos_tol=lanczos_tol)
+    o = abi.IdmrgOpts()
+    o.sweep = _engine.sweep_opts(**kw)
+    o.cell_sites, o.window_dN, o.tol = T, dNw, float(tol)
+    o.min_steps, o.maxiter, o.sweeps_per_step, o.warm_start = int(min_steps), int(maxiter), int(sweeps_per_step), int(bool(warm_start))
+    h = C.c_void_p()
+    abi.check(lib, lib.htn_idmrg_create(ops.ctx, cmpo.handle, C.byref(o), C.byref(h)), "htn_idmrg_create")
+    history, n_sweeps = [], 0
+    try:
+        st = abi.IdmrgStats()
+        needs = True
+        while True:
+            it = len(history)
+            if needs:
+                bL, bR = boundary_table(lib, h, 0), boundary_table(lib, h, 1)
+                bonds, tensors = mps.random_window(W, bL, bR, init_dimension, seed=seed + it, sym=sym)
+                tab = _engine.state_tables(bonds, tensors)
+                rc = lib.htn_idmrg_step(h, *tab.pointers(), C.byref(st))
+            else:
+                rc = lib.htn_idmrg_step(h, None, None, None, None, None, None, C.byref(st))
+            chk = getattr(ops, "check_exchange", None)
+            if chk is not None:
+                chk()
+            abi.check(lib, rc, "htn_idmrg_step")
+            history.append((st.energy_per_site, st.delta))
+            n_sweeps += st.sweeps
+            if verbosity:
+                print(f"IDMRG2 step {it + 1}: sites {W * (it + 1)}  E/site = {st.energy_per_site:.10f}  delta = {st.delta:.3e}  "
+                      f"chi = {st.chi_full}")
+            if st.finished:
+                break
+            needs = bool(st.needs_window)
+        win = C.c_void_p()
+        abi.check(lib, lib.htn_idmrg_window(h, C.byref(win)), "htn_idmrg_window")
+    finally:
+        lib.htn_idmrg_destroy(h)
+    eng = _engine.DMRG2.wrap(ops, cmpo, win, **kw)
+    eng.energy = st.energy
+    boundary = {"bL": dict(eng.bond(0).dims), "bR": dict(eng.bond(W).dims), "Lenv": eng.env_data("L", 0),
+                "Renv": eng.env_data("R", W)}
+    return IDMRGResult(energy_per_site=st.energy_per_site, delta=st.delta, iterations=len(history), unit_cell=T,
+                       bond_dims=eng.bond_dims(), spectrum=eng.spectrum(T), history=history, engine=eng, boundary=boundary,
+                       sweeps=n_sweeps)
+
+
+def boundary_table(lib, handle, side) -> dict:
+    """{sector: count} the next window of an htn_idmrg driver must have at its left (0) / right (1) end"""
+    n = lib.htn_idmrg_boundary(handle, side, None)
+    if n < 0:
+        raise abi.HtnError("htn_idmrg_boundary: bad argument")
+    arr = np.zeros(max(n, 1), dtype=abi.SECTOR_DT)
+    lib.htn_idmrg_boundary(handle, side, arr.ctypes.data)
+    return {(int(r["N"]), int(r["j"])): int(r["count"]) for r in arr[:n]}
 
 
 def _absorb(eng, T, sym, dNw, carry):

@@ -401,6 +401,53 @@ int32_t htn_balance_tiles(const htn_tile* tiles_host, int32_t n_tiles, int32_t n
 /* plan-cache statistics: hits, misses (host planner invocations) */
 int htn_mps_cache_stats(const htn_mps* mps, int64_t* hits, int64_t* misses);
 
+/* =====================================================================================================
+ * Infinite chain: step-wise IDMRG2 driver (McCulloch's growing window, arXiv:0804.2509), what sits behind
+ *     find_groundstate(psi0::InfiniteMPS, H, IDMRG2(; trscheme, tol))        src/HubbardFunctions.jl:1010
+ * A window of 2T sites (window_mpo, full-width MPO bonds at both ends) is optimised by two-site sweeps between two
+ * boundary environments; its halves are then absorbed into the boundaries (the environments at the centre bond; the
+ * right one relabelled N -> N + window_dN) and the next window is predicted from the previous one's halves.  Boundary
+ * environments and site tensors stay on the device from one step to the next.
+ * The host supplies random windows (initialize_mps stays on the host side): a step whose previous step returned
+ * needs_window = 1 (and the first step) must be given one, built between the tables htn_idmrg_boundary reports.
+ * Handles are reference counted like htn_mps: the driver keeps its context and MPO alive; htn_idmrg_window hands out a
+ * new reference to the current window (release it with htn_mps_destroy), valid after htn_idmrg_destroy.
+ * ===================================================================================================== */
+typedef struct htn_idmrg htn_idmrg;
+typedef struct {
+    htn_sweep_opts sweep;      /* truncation + solver of every window update                                          */
+    int32_t cell_sites;        /* T: the window MPO holds 2T sites                                                    */
+    int32_t window_dN;         /* particles per window, 2T P / Q (HTN_SYM_SU2: its parity)                            */
+    double tol;                /* stop when the change of the centre spectrum delta < tol ...                         */
+    int32_t min_steps;         /* ... after at least min_steps steps                                                  */
+    int32_t maxiter;           /* or after maxiter steps                                                              */
+    int32_t sweeps_per_step;   /* window sweeps per step (at most; early exit when the energy has settled)            */
+    int32_t warm_start;        /* 1: McCulloch prediction from the third window on; 0: every window from the host     */
+} htn_idmrg_opts;              /* 96 bytes */
+typedef struct {
+    int32_t step;              /* 0-based index of the step just run                                                  */
+    int32_t sweeps;            /* window sweeps of this step                                                          */
+    int32_t converged;         /* delta < tol after at least min_steps steps                                          */
+    int32_t finished;          /* converged or maxiter reached: no further step (the window stays as its sweeps left it) */
+    int32_t needs_window;      /* the next step must be given a window from the host                                  */
+    int32_t chi_full;          /* TensorKit dim of the centre bond                                                    */
+    double energy;             /* <psi|H|psi> of the grown system (all absorbed sites + the window)                   */
+    double energy_per_site;    /* (energy - previous energy) / 2T; NaN on step 0                                      */
+    double delta;              /* qdim-weighted distance of the centre spectra of this and the previous step; inf on step 0 */
+} htn_idmrg_stats;             /* 48 bytes */
+int htn_idmrg_create(htn_ctx* ctx, const htn_mpo* window_mpo, const htn_idmrg_opts* opts, htn_idmrg** out);
+void htn_idmrg_destroy(htn_idmrg* idmrg);
+/* bond table the next window must have at its left (side 0) / right (side 1) end; two-call pattern (NULL: count only).
+ * -> number of sectors, -1 on a bad argument */
+int32_t htn_idmrg_boundary(const htn_idmrg* idmrg, int32_t side, htn_sector* sectors_host);
+/* one growth step.  Window tables as in htn_mps_create (bond_ptr ... data, 2T sites); all NULL = start from the driver's
+ * prediction (allowed only when the previous step returned needs_window = 0).  stats_host may be NULL. */
+int htn_idmrg_step(htn_idmrg* idmrg, const int32_t* bond_ptr_host, const htn_sector* sectors_host,
+                   const int32_t* sub_ptr_host, const htn_subblock* subs_host, const int64_t* data_ptr_host,
+                   const void* data_host, htn_idmrg_stats* stats_host);
+/* the current window as an htn_mps (a new reference: release it with htn_mps_destroy) */
+int htn_idmrg_window(htn_idmrg* idmrg, htn_mps** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@
 # they are; their results are exported as tables, the sweeps run in the library, the state is imported back.
 module HubbardHIP
 
-using MPSKit, TensorKit, BlockTensorKit
+using MPSKit, TensorKit, BlockTensorKit, Random
 using TensorKit: FusionTree, fusiontrees, sectors, dim, space, domain, codomain
 
 const lib = "libhubbardtn_hip.so"
@@ -108,12 +108,12 @@ end
 # centre tensor x̃ = sqrt(2S_c + 1) t_c with c the RIGHT sector for AC and for right-canonical tensors.  The factor is
 # applied to a copy of the data vector below.  UNVERIFIED against TensorKit's Clebsch-Gordan phase convention: validate once
 # on a small state (norm, energy and singular values do not depend on it).
-function export_mps(ψ::FiniteMPS, P::Int, Q::Int)
+function export_mps(ψ::FiniteMPS, P::Int, Q::Int; offset::Int = 0)     # offset: sites left of bond 0 (iDMRG window)
     L = length(ψ)
     bond_ptr, secs = Int32[0], HtnSector[]
     for b in 0:L
         V = b == 0 ? left_virtualspace(ψ, 1) : right_virtualspace(ψ, b)
-        labs = sort([(label(c, P, Q, b)..., Int32(dim(V, c))) for c in sectors(V)])
+        labs = sort([(label(c, P, Q, b + offset)..., Int32(dim(V, c))) for c in sectors(V)])
         append!(secs, (HtnSector(l...) for l in labs))
         push!(bond_ptr, Int32(length(secs)))
     end
@@ -131,8 +131,8 @@ function export_mps(ψ::FiniteMPS, P::Int, Q::Int)
             for col in 0:n_c-1, row in 0:n_a-1
                 d[sv.offset + 1 + row + col * ld] *= scale
             end
-            lN, lj = label(a, P, Q, i - 1)
-            rN, rj = label(c, P, Q, i)
+            lN, lj = label(a, P, Q, i - 1 + offset)
+            rN, rj = label(c, P, Q, i + offset)
             push!(subs, HtnSubblock(lN, lj, Int32(site_index(s, P, Q) - 1), rN, rj, Int32(ld), Int64(sv.offset)))
         end
         append!(data, d)
@@ -145,7 +145,7 @@ end
 # ---- MPS import: htn_mps_bond / htn_mps_site_size / htn_mps_get_site per site -----------------------------------------
 # Builds new virtual spaces from the bond tables the library returns, allocates TensorMaps on them and copies every
 # sub-block into its fusion-tree window (undoing the tilde factor).  The centre is on site 1 after htn_dmrg2_sweep.
-function import_mps(mps::Ptr{Cvoid}, ψ::FiniteMPS, P::Int, Q::Int)
+function import_mps(mps::Ptr{Cvoid}, ψ::FiniteMPS, P::Int, Q::Int; offset::Int = 0)
     L = length(ψ)
     I = sectortype(ψ.AC[1])
     bond(b) = begin
@@ -154,7 +154,7 @@ function import_mps(mps::Ptr{Cvoid}, ψ::FiniteMPS, P::Int, Q::Int)
         ccall((:htn_mps_bond, lib), Int32, (Ptr{Cvoid}, Int32, Ptr{HtnSector}), mps, b, out)
         out
     end
-    sector(rec::HtnSector, b) = I(isodd(rec.N), rec.j // 2, rec.N * Q - P * b)      # (parity, S, shifted charge)
+    sector(rec::HtnSector, b) = I(isodd(rec.N), rec.j // 2, rec.N * Q - P * (b + offset))      # (parity, S, shifted charge)
     spaces = [Vect[I]((sector(r, b) => Int(r.count) for r in bond(b))...) for b in 0:L]
     phys = physicalspace(ψ, 1)
     tensors = map(1:L) do i
@@ -168,7 +168,7 @@ function import_mps(mps::Ptr{Cvoid}, ψ::FiniteMPS, P::Int, Q::Int)
         for (f1, f2) in fusiontrees(A)
             a, s = f1.uncoupled
             c = f2.uncoupled[1]
-            key = (label(a, P, Q, i - 1)..., Int32(site_index(s, P, Q) - 1), label(c, P, Q, i)...)
+            key = (label(a, P, Q, i - 1 + offset)..., Int32(site_index(s, P, Q) - 1), label(c, P, Q, i + offset)...)
             haskey(table, key) || continue
             sb = table[key]
             sv = A[f1, f2]
@@ -197,8 +197,8 @@ end
 # its value IS the reduced element up to the recoupling factor the planner applies itself.  UNVERIFIED: whether TensorKit's
 # (V_j ⊗ P ← P ⊗ V_k) tree basis needs an F-move to reach the library's <out|| O ||in> with the level spin coupled from the
 # left (DESIGN.md section 2); for rank-0 operators (number, double occupancy, identity) no recoupling arises.
-function export_mpo(H, P::Int, Q::Int)
-    L = length(H)
+function export_mpo(H, P::Int, Q::Int; L::Int = length(H))       # L > length(H): periodic continuation (iDMRG window)
+
     sym = HtnSymmetry(0, 3, (0, 1, 2, 0), (0, 1, 0, 0))          # HTN_SYM_SU2_U1: site multiplets (N, 2S) = (0,0), (1,1), (2,0)
     ops = HtnSiteOp[]
     opindex = Dict{Tuple{Int32,Int32,NTuple{16,Float64}},Int32}()
@@ -289,6 +289,120 @@ end
 
 # In compute_groundstate (src/HubbardFunctions.jl:1010) a finite-chain run then reads
 #     ψ, envs, δ = find_groundstate(ψ₀, H, HubbardHIP.HIPDMRG2(; trscheme = truncbelow(10.0^(-svalue)), tol = tol, P = P, Q = Q))
-# The infinite-chain IDMRG2 the reference hard-codes needs the growing-window loop of hubbardtn_amd/idmrg.py on this side
-# (htn_mps_create with boundary environments, htn_mps_get_env / htn_mps_env_bond); it is not written here.
+
+# ---- infinite chain: the library's IDMRG2 driver (htn_idmrg_*) ------------------------------------------------------------
+# UNTESTED like everything in this file (no Julia in the build image).  The same protocol is exercised from Python by
+# tests/test_idmrg_native_cpu.py (C ABI only) and hubbardtn_amd/idmrg.py (_native_idmrg2).
+# The growth loop runs in the library: the window of 2T sites (T = length(H)) is swept between two device-resident boundary
+# environments, absorbed, and the next window predicted.  This side only supplies the random windows the driver asks for
+# (needs_window), built with TensorKit between the boundary tables htn_idmrg_boundary reports, and imports the last window.
+struct HtnIdmrgOpts
+    sweep::HtnSweepOpts
+    cell_sites::Int32
+    window_dN::Int32
+    tol::Float64
+    min_steps::Int32
+    maxiter::Int32
+    sweeps_per_step::Int32
+    warm_start::Int32
+end
+struct HtnIdmrgStats
+    step::Int32
+    sweeps::Int32
+    converged::Int32
+    finished::Int32
+    needs_window::Int32
+    chi_full::Int32
+    energy::Float64
+    energy_per_site::Float64
+    delta::Float64
+end
+
+struct HIPIDMRG2{T} <: MPSKit.Algorithm
+    trscheme::T
+    tol::Float64
+    maxiter::Int
+    krylovdim::Int
+    sweeps_per_step::Int
+    P::Int
+    Q::Int
+end
+HIPIDMRG2(; trscheme, tol = 1e-6, maxiter = 100, krylovdim = 30, sweeps_per_step = 6, P = 1, Q = 1) =
+    HIPIDMRG2(trscheme, tol, maxiter, krylovdim, sweeps_per_step, P, Q)
+
+# a random window of L sites between the boundary tables bL / bR (library labels; `offset` sites to the left of the window):
+# inner spaces = what the left table reaches and the right one co-reaches (capped at D per sector, as initialize_mps),
+# tensors random; FiniteMPS brings sites 2.. into right-canonical form
+function random_window(bL, bR, L::Int, D::Int, offset::Int, P::Int, Q::Int, phys)
+    I = sectortype(phys)
+    sec(rec, b) = I(isodd(rec.N), rec.j // 2, rec.N * Q - P * (b + offset))
+    VL = Vect[I]((sec(r, 0) => Int(r.count) for r in bL)...)
+    VR = Vect[I]((sec(r, L) => Int(r.count) for r in bR)...)
+    fwd = [VL]
+    for i in 1:L
+        push!(fwd, fuse(fwd[end] ⊗ phys))
+    end
+    bwd = [VR]
+    for i in L:-1:1
+        pushfirst!(bwd, fuse(bwd[1] ⊗ phys'))
+    end
+    spaces = [i == 0 ? VL : i == L ? VR : infimum(infimum(fwd[i+1], bwd[i+1]), Vect[I]((c => D for c in sectors(fwd[i+1]))...)) for i in 0:L]
+    tensors = [randn(ComplexF64, spaces[i] ⊗ phys, spaces[i+1]) for i in 1:L]
+    return FiniteMPS(tensors; normalize = false)
+end
+
+function MPSKit.find_groundstate(ψ::InfiniteMPS, H, alg::HIPIDMRG2, envs = nothing; init_dimension = 8, seed = 1234)
+    T = length(H)
+    (2T * alg.P) % alg.Q == 0 || error("HIPIDMRG2: 2T P / Q is not an integer")
+    ctx, mpo, drv, win = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:htn_ctx_create, lib), Cint, (Int32, Int32, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), 1, 0, C_NULL, ctx))
+    try
+        sym, ops, level_ptr, levels, entry_ptr, entries = export_mpo(H, alg.P, alg.Q; L = 2T)
+        check(ccall((:htn_mpo_create, lib), Cint,
+            (Ptr{Cvoid}, Ref{HtnSymmetry}, Int32, Ptr{HtnSiteOp}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{HtnMpoEntry}, Ref{Ptr{Cvoid}}),
+            ctx[], sym, 2T, ops, length(ops), level_ptr, levels, entry_ptr, entries, mpo))
+        opts = HtnIdmrgOpts(sweep_opts(alg.trscheme; krylovdim = alg.krylovdim), Int32(T), Int32(2T * alg.P ÷ alg.Q), alg.tol,
+                            Int32(3), Int32(alg.maxiter), Int32(alg.sweeps_per_step), Int32(1))
+        check(ccall((:htn_idmrg_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{HtnIdmrgOpts}, Ref{Ptr{Cvoid}}), ctx[], mpo[], opts, drv))
+        boundary(side) = begin
+            n = ccall((:htn_idmrg_boundary, lib), Int32, (Ptr{Cvoid}, Int32, Ptr{HtnSector}), drv[], side, C_NULL)
+            out = Vector{HtnSector}(undef, n)
+            ccall((:htn_idmrg_boundary, lib), Int32, (Ptr{Cvoid}, Int32, Ptr{HtnSector}), drv[], side, out)
+            out
+        end
+        st, needs, step = Ref(HtnIdmrgStats(0, 0, 0, 0, 0, 0, 0.0, NaN, Inf)), true, 0
+        phys = physicalspace(ψ, 1)
+        while true
+            if needs                   # labels of the window: N counted from the left end of the grown chain (step * T sites)
+                Random.seed!(seed + step)
+                w = random_window(boundary(0), boundary(1), 2T, init_dimension, step * T, alg.P, alg.Q, phys)
+                bond_ptr, sectors_, sub_ptr, subs, data_ptr, data = export_mps(w, alg.P, alg.Q; offset = step * T)
+                check(ccall((:htn_idmrg_step, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Int32}, Ptr{HtnSector}, Ptr{Int32}, Ptr{HtnSubblock}, Ptr{Int64}, Ptr{ComplexF64}, Ref{HtnIdmrgStats}),
+                    drv[], bond_ptr, sectors_, sub_ptr, subs, data_ptr, data, st))
+            else
+                check(ccall((:htn_idmrg_step, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Int32}, Ptr{HtnSector}, Ptr{Int32}, Ptr{HtnSubblock}, Ptr{Int64}, Ptr{ComplexF64}, Ref{HtnIdmrgStats}),
+                    drv[], C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, st))
+            end
+            st[].finished != 0 && break
+            needs = st[].needs_window != 0
+            step += 1
+        end
+        check(ccall((:htn_idmrg_window, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), drv[], win))
+        # the last window as a FiniteMPS (its central unit cell is the converged cell: sites T/2+1 .. T/2+T), the energy
+        # density and the last change of the centre spectrum
+        template = random_window(boundary(0), boundary(1), 2T, 1, step * T, alg.P, alg.Q, phys)
+        ψw = import_mps(win[], template, alg.P, alg.Q; offset = step * T)
+        return ψw, st[].energy_per_site, st[].delta
+    finally            # handles are reference counted: any order is safe
+        win[] == C_NULL || ccall((:htn_mps_destroy, lib), Cvoid, (Ptr{Cvoid},), win[])
+        drv[] == C_NULL || ccall((:htn_idmrg_destroy, lib), Cvoid, (Ptr{Cvoid},), drv[])
+        mpo[] == C_NULL || ccall((:htn_mpo_destroy, lib), Cvoid, (Ptr{Cvoid},), mpo[])
+        ccall((:htn_ctx_destroy, lib), Cvoid, (Ptr{Cvoid},), ctx[])
+    end
+end
+# compute_groundstate's infinite-chain call (src:1010) then reads
+#     ψw, e, δ = find_groundstate(ψ₀, H, HubbardHIP.HIPIDMRG2(; trscheme = truncbelow(10.0^(-svalue)), tol = tol, P = P, Q = Q))
+# with e the energy per site the reference's expectation_value(ψ, H) / length(H) reports.
 end # module
