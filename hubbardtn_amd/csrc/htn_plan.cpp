@@ -1047,6 +1047,8 @@ void plan_right_env(const Mpo& mpo, const EnvLayout& Rl, const SiteLayout& lay, 
 // R^H, returning (isometry x Sigma) directly.  Blocks with a side > 512 fall back to the plain staging: mode A stages
 // the block so that the normalised Jacobi output IS the wanted isometry; mode B (block much wider than tall in that
 // orientation) orthogonalises the short side instead and accumulates the rotation J, which then is the isometry.
+// A block above 512 in both orientations is staged in mode A like any other; its columns are longer than one
+// workgroup's registers hold, and the kernel gives it the multi-CU pair-visit path with row-chunked columns.
 int plan_svd(const ThetaLayout& tl, bool right, SvdPlan& out) {
     const size_t n = tl.mats.size();
     out = SvdPlan();
@@ -1102,7 +1104,6 @@ int plan_svd(const ThetaLayout& tl, bool right, SvdPlan& out) {
         } else {
             m = nA, nn = mA, tr = right, acc = true;
         }
-        if (m > 512) return set_error("coupled block taller than 512 rows in both orientations (%d x %d)", rows, cols);
         d.g_off = go;
         d.v_off = vo;
         d.s_off = so;

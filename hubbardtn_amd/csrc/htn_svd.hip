@@ -1566,6 +1566,267 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_finish(double2* __restri
     if (tid == 0) info[b] = done[blockIdx.x] ? sweeps[blockIdx.x] : -sweeps[blockIdx.x];
 }
 
+// ---- tall blocks: pair-visit block Jacobi with the columns streamed from global memory ------------------------------
+// A plain (non-QRCP) block whose columns are longer than 512 rows fits neither the registers of the one-workgroup kernel
+// nor the LDS panel of k_jacobi_pairs_gram.  It runs the same tournament as the pair-visit path (one launch per round,
+// one workgroup per panel pair, the launch boundary the only ordering between workgroups, no workgroup ever waits for
+// another), but a visit never holds its 16 columns: (a) the 16 x 16 Gram is accumulated on v_mfma_f64_16x16x4_f64 over
+// row chunks read straight from global memory, every wave a contiguous row range, the wave partials summed in a fixed
+// order; (b) the inner two-sided Jacobi and the convergence measure are those of k_jacobi_pairs_gram (a copy, so that
+// kernel's code generation does not move); (c) U is applied chunk by chunk to the columns of X and, when accumulating,
+// to the same columns of J (n x n, ld n).  No QR preconditioning: expect more outer sweeps than the QRCP path.
+#define TALL_THREADS 512
+#define TALL_WAVES (TALL_THREADS / 64)
+#define TALL_DEPTH 8              // loads in flight per lane: k-steps of the Gram, 16-row tiles (x 4 columns) of the apply
+#define TALL_PARTS 32             // workgroups per block of the |X|_F^2 / identity-J pass
+
+// slot q (0..15) of a visit -> column index, -1 for dead slots
+__device__ __forceinline__ int tall_col(const JacPairItem& it, int q) {
+    return q < 8 ? (q < it.ni ? it.ci + q : -1) : (q - 8 < it.nj ? it.cj + (q - 8) : -1);
+}
+
+// A[:, cols] <- A[:, cols] U for a rows x n matrix with leading dimension ld (U: 16 x 16 in LDS, ld JG_LD).
+// Same transposed MFMA product as step (3) of k_jacobi_pairs_gram, B operand read from global memory: a wave owns
+// 16-row tiles rt = wave + TALL_WAVES t, so no two waves touch the same rows.
+__device__ __forceinline__ void tall_apply(double2* A, int64_t ld, int rows, const double2* Uc, const JacPairItem& it,
+                                           int wave, int l15, int l4) {
+    double ur[4], ui[4], nui[4];
+    int colk[4], colg[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        const double2 u = Uc[(4 * kk + l4) * JG_LD + l15];
+        ur[kk] = u.x;
+        ui[kk] = u.y;
+        nui[kk] = -u.y;
+        colk[kk] = tall_col(it, 4 * kk + l4);        // B operand: column slot 4 kk + l4
+        colg[kk] = tall_col(it, l4 + 4 * kk);        // output row r of the accumulator: column slot l4 + 4 r
+    }
+    const int nrt = (rows + 15) >> 4;
+    for (int rt0 = wave; rt0 < nrt; rt0 += TALL_WAVES * (TALL_DEPTH / 4)) {
+        double2 p[TALL_DEPTH / 4][4];
+#pragma unroll
+        for (int t = 0; t < TALL_DEPTH / 4; ++t) {
+            const int row = (rt0 + t * TALL_WAVES) * 16 + l15;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                p[t][kk] = (colk[kk] >= 0 && row < rows) ? A[(int64_t)colk[kk] * ld + row] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int t = 0; t < TALL_DEPTH / 4; ++t) {
+            const int row = (rt0 + t * TALL_WAVES) * 16 + l15;
+            d4 ar = {0.0, 0.0, 0.0, 0.0}, ai = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                ar = __builtin_amdgcn_mfma_f64_16x16x4f64(ur[kk], p[t][kk].x, ar, 0, 0, 0);
+                ai = __builtin_amdgcn_mfma_f64_16x16x4f64(ur[kk], p[t][kk].y, ai, 0, 0, 0);
+                ar = __builtin_amdgcn_mfma_f64_16x16x4f64(nui[kk], p[t][kk].y, ar, 0, 0, 0);
+                ai = __builtin_amdgcn_mfma_f64_16x16x4f64(ui[kk], p[t][kk].x, ai, 0, 0, 0);
+            }
+            if (row < rows) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (colg[r] >= 0) A[(int64_t)colg[r] * ld + row] = make_double2(ar[r], ai[r]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(TALL_THREADS) void k_jacobi_tall_visit(double2* __restrict__ G, double2* __restrict__ Vj,
+                                                                    const htn_svd_block* __restrict__ desc,
+                                                                    const int* __restrict__ tall_ids,
+                                                                    const JacPairItem* __restrict__ items,
+                                                                    const double* __restrict__ zero2,
+                                                                    unsigned long long* __restrict__ ratio_bits,
+                                                                    const int* __restrict__ done, double tol) {
+    __shared__ double s_part[TALL_WAVES * 64 * JG_PS];      // Gram partials of every wave
+    __shared__ double2 GU[4 * 16 * JG_LD];                   // G[2][16][17], U[2][16][17]
+    __shared__ unsigned long long s_rbits;
+    const JacPairItem it = items[blockIdx.x];
+    if (done[it.blk]) return;
+    const htn_svd_block D = desc[tall_ids[it.blk]];
+    const int m = D.m, n = D.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
+    double2* X = G + D.g_off;
+    const int mode = it.pad[0], nrounds = mode ? 7 : 8;
+    const double z2 = zero2[it.blk];
+    const double tol2 = tol * tol;
+    if (tid == 0) s_rbits = 0ull;
+    // ---- (a) Gram: lane (l15, l4) feeds row 4 ks + l4 of column slot l15 as A and as B operand; wave w sums the
+    //      k-steps [w per, (w + 1) per) in ascending order ----
+    {
+        d4 g1 = {0.0, 0.0, 0.0, 0.0}, g2 = {0.0, 0.0, 0.0, 0.0}, mm = {0.0, 0.0, 0.0, 0.0};
+        const int col = tall_col(it, l15);
+        const double2* src = X + (int64_t)(col >= 0 ? col : 0) * m;
+        const int nks = (m + 3) >> 2, per = (nks + TALL_WAVES - 1) / TALL_WAVES;
+        const int ks0 = wave * per, ks1 = min(nks, ks0 + per);
+        for (int ks = ks0; ks < ks1; ks += TALL_DEPTH) {
+            double2 v[TALL_DEPTH];
+#pragma unroll
+            for (int u = 0; u < TALL_DEPTH; ++u) {
+                const int row = 4 * (ks + u) + l4;
+                v[u] = (col >= 0 && ks + u < ks1 && row < m) ? src[row] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < TALL_DEPTH; ++u) {
+                if (ks + u < ks1) {                  // wave-uniform
+                    g1 = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u].x, v[u].x, g1, 0, 0, 0);
+                    g2 = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u].y, v[u].y, g2, 0, 0, 0);
+                    mm = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u].x, v[u].y, mm, 0, 0, 0);      // M[a][b] = sum re_a im_b
+                }
+            }
+        }
+        double* part = s_part + (wave * 64 + lane) * JG_PS;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            part[r] = g1[r] + g2[r];
+            part[4 + r] = mm[r];
+        }
+    }
+    __syncthreads();
+    // threads 256.. mirror 0..255 (same element, same arithmetic) and never write G / U
+    const bool el = tid < 256;
+    const int ei = (tid >> 4) & 15, ej = tid & 15;
+    {
+        // accumulator element (row = l4 + 4 reg, col = l15): G[i][j] sits in lane j + 16 (i & 3), reg i >> 2
+        const double* pa = s_part + (ej + 16 * (ei & 3)) * JG_PS + (ei >> 2);
+        const double* pb = s_part + (ei + 16 * (ej & 3)) * JG_PS + 4 + (ej >> 2);
+        double gr = 0.0, mij = 0.0, mji = 0.0;
+#pragma unroll
+        for (int w = 0; w < TALL_WAVES; ++w) {      // fixed order: deterministic
+            gr += pa[w * 64 * JG_PS];
+            mij += pa[w * 64 * JG_PS + 4];
+            mji += pb[w * 64 * JG_PS];
+        }
+        if (el) {
+            GU[ei * JG_LD + ej] = make_double2(gr, mij - mji);
+            GU[2 * 16 * JG_LD + ei * JG_LD + ej] = make_double2(ei == ej ? 1.0 : 0.0, 0.0);
+        }
+    }
+    __syncthreads();
+    // ---- convergence measure of this visit: max squared cosine over its column pairs (exact Gram) ----
+    {
+        double ratio = 0.0;
+        const bool vi = ei < 8 ? ei < it.ni : ei - 8 < it.nj, vj = ej < 8 ? ej < it.ni : ej - 8 < it.nj;
+        if (vi && vj && ei < ej && (mode ? (ei >> 3) == (ej >> 3) : (ei < 8 && ej >= 8))) {
+            const double dii = GU[ei * JG_LD + ei].x, djj = GU[ej * JG_LD + ej].x;
+            const double2 g = GU[ei * JG_LD + ej];
+            if (dii > z2 && djj > z2) ratio = fma(g.x, g.x, g.y * g.y) * fast_rcp(dii * djj);
+        }
+        const unsigned long long key = wave_max_u64((unsigned long long)__double_as_longlong(ratio));
+        if (lane == 0 && key) atomicMax(&s_rbits, key);
+    }
+    __syncthreads();
+    const unsigned long long first_bits = s_rbits;
+    if (__longlong_as_double((long long)first_bits) <= tol2) {     // nothing to rotate in this visit (uniform)
+        if (tid == 0 && first_bits) atomicMax(&ratio_bits[it.blk], first_bits);
+        return;
+    }
+    // ---- (b) two-sided Jacobi on G, U <- U J: one cyclic sweep, as in k_jacobi_pairs_gram ----
+    unsigned livemask = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) livemask |= (unsigned)(q < 8 ? q < it.ni : q - 8 < it.nj) << q;
+    int cur = 0;
+    for (int r = 0; r < nrounds; ++r) {
+        const double2* Gc = GU + cur * 16 * JG_LD;
+        const double2* Uc = GU + (2 + cur) * 16 * JG_LD;
+        double2* Gn = GU + (cur ^ 1) * 16 * JG_LD;
+        double2* Un = GU + (2 + (cur ^ 1)) * 16 * JG_LD;
+        const int ib = jg_partner(ei, r, mode), jb = jg_partner(ej, r, mode);
+        const int ilo = ei < ib ? ei : ib, ihi = ei < ib ? ib : ei;
+        const int jlo = ej < jb ? ej : jb, jhi = ej < jb ? jb : ej;
+        const double iaa = Gc[ilo * JG_LD + ilo].x, ibb = Gc[ihi * JG_LD + ihi].x;
+        const double2 ig = Gc[ilo * JG_LD + ihi];                  // conj(a_lo) . a_hi
+        const double jaa = Gc[jlo * JG_LD + jlo].x, jbb = Gc[jhi * JG_LD + jhi].x;
+        const double2 jg = Gc[jlo * JG_LD + jhi];
+        const double2 gij = Gc[ei * JG_LD + ej], gijb = Gc[ei * JG_LD + jb];
+        const double2 gibj = Gc[ib * JG_LD + ej], gibjb = Gc[ib * JG_LD + jb];
+        const double2 uij = Uc[ei * JG_LD + ej], uijb = Uc[ei * JG_LD + jb];
+        double ci, cqi, dqi, cj, cqj, dqj;
+        const bool oni = jg_rotation(iaa, ibb, ig, ((livemask >> ilo) & (livemask >> ihi) & 1u) != 0, z2, tol2, ci, cqi, dqi);
+        jg_rotation(jaa, jbb, jg, ((livemask >> jlo) & (livemask >> jhi) & 1u) != 0, z2, tol2, cj, cqj, dqj);
+        const double2 jpj = ej == jlo ? make_double2(-cqj * jg.x, cqj * jg.y) : make_double2(cqj * jg.x, cqj * jg.y);
+        const double2 ipi = ei == ilo ? make_double2(-cqi * ig.x, cqi * ig.y) : make_double2(cqi * ig.x, cqi * ig.y);
+        double2 t2 = cmul(gijb, jpj);
+        const double2 Tij = make_double2(fma(cj, gij.x, t2.x), fma(cj, gij.y, t2.y));
+        t2 = cmul(gibjb, jpj);
+        const double2 Tibj = make_double2(fma(cj, gibj.x, t2.x), fma(cj, gibj.y, t2.y));
+        t2 = cmulc(ipi, Tibj);
+        double2 gn = make_double2(fma(ci, Tij.x, t2.x), fma(ci, Tij.y, t2.y));
+        {               // pivot block by Rutishauser's formulas: a' = a - t|g|, b' = b + t|g|, off-diagonal 0
+            const double dg = ei == ilo ? iaa - dqi : ibb + dqi;
+            const bool pd = oni && ej == ei, po = oni && ej == ib;
+            gn.x = pd ? dg : (po ? 0.0 : gn.x);
+            gn.y = (pd || po) ? 0.0 : gn.y;
+        }
+        t2 = cmul(uijb, jpj);
+        if (el) {
+            Gn[ei * JG_LD + ej] = gn;
+            Un[ei * JG_LD + ej] = make_double2(fma(cj, uij.x, t2.x), fma(cj, uij.y, t2.y));
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    // ---- (c) X[:, pair] <- X[:, pair] U, and J[:, pair] <- J[:, pair] U when accumulating ----
+    const double2* Uf = GU + (2 + cur) * 16 * JG_LD;
+    tall_apply(X, m, m, Uf, it, wave, l15, l4);
+    if (D.flags & HTN_SVD_ACCUMULATE) tall_apply(Vj + D.v_off, n, n, Uf, it, wave, l15, l4);
+    if (tid == 0) atomicMax(&ratio_bits[it.blk], first_bits);
+}
+
+// |X|_F^2 of every tall block in TALL_PARTS column stripes (fixed-order sums: bit-reproducible), J = identity when
+// accumulating; grid (n_tall, TALL_PARTS), 256 threads
+__global__ __launch_bounds__(256) void k_jacobi_tall_init(double2* __restrict__ G, double2* __restrict__ Vj,
+                                                          const htn_svd_block* __restrict__ desc,
+                                                          const int* __restrict__ tall_ids, double* __restrict__ part) {
+    __shared__ double s_w[4];
+    const htn_svd_block D = desc[tall_ids[blockIdx.x]];
+    const int m = D.m, n = D.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double2* __restrict__ X = G + D.g_off;
+    double f = 0.0;
+    for (int j = blockIdx.y; j < n; j += TALL_PARTS)
+        for (int i = tid; i < m; i += 256) {
+            const double2 x = X[(int64_t)j * m + i];
+            f += x.x * x.x + x.y * x.y;
+        }
+    if (D.flags & HTN_SVD_ACCUMULATE) {
+        double2* __restrict__ J = Vj + D.v_off;
+        for (int j = blockIdx.y; j < n; j += TALL_PARTS)
+            for (int i = tid; i < n; i += 256) J[(int64_t)j * n + i] = make_double2(i == j ? 1.0 : 0.0, 0.0);
+    }
+    f = wave_sum(f);
+    if (lane == 0) s_w[wave] = f;
+    __syncthreads();
+    if (tid == 0) part[blockIdx.x * TALL_PARTS + blockIdx.y] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// "numerically zero" threshold of every tall block: 1e-30 |X|_F^2, as in k_jacobi_svd
+__global__ void k_jacobi_tall_zero(const double* __restrict__ part, double* __restrict__ zero2, int nt) {
+    for (int li = threadIdx.x; li < nt; li += blockDim.x) {
+        double t = 0.0;
+        for (int q = 0; q < TALL_PARTS; ++q) t += part[li * TALL_PARTS + q];
+        zero2[li] = 1e-30 * t;
+    }
+}
+
+// S = column norms, info = sweep count (< 0: not converged); grid (ceil(max n / 4), n_tall), one column per wave
+__global__ __launch_bounds__(256) void k_jacobi_tall_finish(const double2* __restrict__ G, double* __restrict__ S,
+                                                            const htn_svd_block* __restrict__ desc,
+                                                            const int* __restrict__ tall_ids,
+                                                            const int* __restrict__ sweeps, const int* __restrict__ done,
+                                                            int* __restrict__ info) {
+    const int b = tall_ids[blockIdx.y];
+    const htn_svd_block D = desc[b];
+    const int m = D.m, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = blockIdx.x * 4 + wave;
+    if (j < D.n) {
+        const double2* __restrict__ x = G + D.g_off + (int64_t)j * m;
+        double sn = 0.0;
+        for (int i = lane; i < m; i += 64) sn += x[i].x * x[i].x + x[i].y * x[i].y;
+        sn = wave_sum(sn);
+        if (lane == 0) S[D.s_off + j] = sqrt(sn);
+    }
+    if (blockIdx.x == 0 && tid == 0) info[b] = done[blockIdx.y] ? sweeps[blockIdx.y] : -sweeps[blockIdx.y];
+}
+
 // =====================================================================================================================
 // Ring block Jacobi: the large blocks' sweeps in ONE launch
 // =====================================================================================================================
@@ -2310,6 +2571,13 @@ struct JacScratch {
     size_t ring_items_cap = 0;
     int cu_count = 0;
     int xcd_local = 0;                  // 1: in the last ring launch every block's workgroups found themselves on one XCD
+    void* tall_dev = nullptr;           // tall-block path: [skip | ids | zero2 | partials | ratio | done | sweeps | items]
+    size_t tall_dev_bytes = 0;
+    void* tall_pin = nullptr;           // its host -> device staging: [items | skip | ids]
+    size_t tall_pin_bytes = 0;
+    int* tall_flags = nullptr;          // device -> host: active tall blocks per sweep; coherent
+    int* tall_flags_dev = nullptr;
+    size_t tall_flags_elems = 0;
     hipStream_t aux = nullptr;          // forked stream: small blocks run beside the large-block pipeline
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_sweep[2] = {nullptr, nullptr};
     ~JacScratch() {
@@ -2330,6 +2598,9 @@ struct JacScratch {
         if (ring_mbox) (void)hipFree(ring_mbox);
         if (ring_items) (void)hipFree(ring_items);
         if (ring_items_h) (void)hipHostFree(ring_items_h);
+        if (tall_dev) (void)hipFree(tall_dev);
+        if (tall_pin) (void)hipHostFree(tall_pin);
+        if (tall_flags) (void)hipHostFree(tall_flags);
     }
 };
 static std::mutex g_js_mu;
@@ -2383,10 +2654,11 @@ static int js_reserve(JacScratch& g_js, size_t dev_bytes, size_t pin_bytes, size
     return 0;
 }
 
-extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_block* desc,
-                                const htn_svd_block* desc_host, int32_t n_blocks, int32_t max_m_host,
-                                int32_t max_sweeps, double tol, int32_t* info_dev, const htn_svd_opts* opts,
-                                void* stream) {
+// every block of at most 512 rows (QRCP or not); skip_dev / skip_host (n_blocks entries, NULL = none): blocks another path
+// owns (the tall blocks), left untouched here
+static int jacobi_svd_core(void* G, void* Vj, double* S, const htn_svd_block* desc, const htn_svd_block* desc_host,
+                           int32_t n_blocks, int32_t max_m_host, int32_t max_sweeps, double tol, int32_t* info_dev,
+                           const htn_svd_opts* opts, void* stream, const int* skip_dev, const unsigned char* skip_host) {
     if (n_blocks <= 0) return 0;
     // per-call settings (ABI 2): nothing process-wide is read or written here
     const int g_jac_split = opts && opts->split_elems > 0 ? opts->split_elems : 0;
@@ -2428,7 +2700,7 @@ extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_bloc
     if (opts && opts->sweeps_used) *opts->sweeps_used = 0;
     if (large.empty()) {
         hipLaunchKernelGGL(k_jacobi_svd, dim3(n_blocks), dim3(JAC_THREADS), lds_elems * sizeof(double2), st, (double2*)G,
-                           (double2*)Vj, S, desc, max_sweeps, tol, info_dev, lds_elems, (const int*)nullptr,
+                           (double2*)Vj, S, desc, max_sweeps, tol, info_dev, lds_elems, skip_dev,
                            g_jac_cut * g_jac_cut);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -2512,7 +2784,7 @@ extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_bloc
     int* d_rank = d_active + (max_sweeps + 1);
     volatile int* h_ring_sw = h_rank + nl;           // ring path: outer sweeps per large block (0: the launch failed)
     int* d_ring_sw = d_rank + nl;
-    for (int b = 0; b < n_blocks; ++b) h_slot[b] = -1;
+    for (int b = 0; b < n_blocks; ++b) h_slot[b] = skip_host && skip_host[b] ? nl : -1;
     for (int li = 0; li < nl; ++li) h_slot[large[li]] = li;
     for (int li = 0; li < nl; ++li) h_ids[li] = large[li];
     for (int k = 0; k <= max_sweeps; ++k) h_active[k] = 1;
@@ -2782,6 +3054,175 @@ extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_bloc
                        d_ids, d_perm, d_sw, d_done, info_dev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(htn_stream_spin(st));      // the pinned staging block is reused by the next call
+    return 0;
+}
+
+// Entry point: blocks of at most 512 rows go to jacobi_svd_core; plain (non-QRCP) blocks with longer columns ("tall") to the
+// streamed pair-visit path above, on the same stream, after the core path has been enqueued (its large blocks finish first)
+extern "C" int htn_jacobi_svd_z(void* G, void* Vj, double* S, const htn_svd_block* desc,
+                                const htn_svd_block* desc_host, int32_t n_blocks, int32_t max_m_host,
+                                int32_t max_sweeps, double tol, int32_t* info_dev, const htn_svd_opts* opts,
+                                void* stream) {
+    if (n_blocks <= 0) return 0;
+    std::vector<int> tall;
+    int max_m_rest = 0;
+    if (desc_host) {
+        for (int b = 0; b < n_blocks; ++b) {
+            const htn_svd_block& D = desc_host[b];
+            if (!(D.flags & HTN_SVD_QRCP) && D.m > 64 * JAC_MAXEL) tall.push_back(b);
+            else max_m_rest = std::max(max_m_rest, std::max(D.m, D.pad));
+        }
+    } else if (max_m_host > 64 * JAC_MAXEL) {
+        return fail_msg("htn_jacobi_svd_z: blocks taller than 512 rows need the host copy of the descriptors (desc_host)");
+    }
+    if (tall.empty())
+        return jacobi_svd_core(G, Vj, S, desc, desc_host, n_blocks, max_m_host, max_sweeps, tol, info_dev, opts, stream,
+                               nullptr, nullptr);
+    if (max_m_rest > 64 * JAC_MAXEL) return fail_msg("htn_jacobi_svd_z: block taller than 512 rows");
+    const int nt = (int)tall.size();
+    hipStream_t st = (hipStream_t)stream;
+    JacScratch* jsp = nullptr;
+    if (js_get(st, &jsp)) return 1;
+    JacScratch& g_js = *jsp;
+    if (js_reserve(g_js, 0, 0, 0)) return 1;         // (creates the sweep events on first use)
+    // the tournament of the pair-visit path: round-robin over panels of JAC_PANEL columns, the intra-panel visits last
+    std::vector<std::vector<JacPairItem>> rounds;
+    {
+        const int w = JAC_PANEL;
+        std::vector<JacPairItem> intra;
+        for (int li = 0; li < nt; ++li) {
+            const int n = desc_host[tall[li]].n;
+            if (n < 1) continue;
+            const int nb = (n + w - 1) / w;
+            const int nbp = nb + (nb & 1);
+            if ((int)rounds.size() < nbp - 1) rounds.resize(nbp - 1);
+            for (int r = 0; r < nbp - 1; ++r)
+                for (int p = 0; p < nbp / 2; ++p) {
+                    int a = p == 0 ? nbp - 1 : (r + p) % (nbp - 1);
+                    int c = p == 0 ? r : (r + nbp - 1 - p) % (nbp - 1);
+                    if (a >= nb || c >= nb) continue;
+                    if (a > c) std::swap(a, c);
+                    JacPairItem it = {li, a * w, std::min(w, n - a * w), c * w, std::min(w, n - c * w), {0, 0, 0}};
+                    rounds[r].push_back(it);
+                }
+            for (int a = 0; a < nb; a += 2) {
+                const int c = a + 1;
+                JacPairItem it = {li, a * w, std::min(w, n - a * w), c < nb ? c * w : 0,
+                                  c < nb ? std::min(w, n - c * w) : 0, {1, 0, 0}};
+                intra.push_back(it);
+            }
+        }
+        rounds.push_back(intra);
+    }
+    size_t n_items = 0;
+    std::vector<size_t> r_off(rounds.size());
+    for (size_t r = 0; r < rounds.size(); ++r) {
+        r_off[r] = n_items;
+        n_items += rounds[r].size();
+    }
+    // device scratch [skip | ids | zero2 | partials | ratio | done | sweeps | items]; ratio | done | sweeps zeroed as one
+    const size_t off_skip = 0, off_ids = off_skip + sizeof(int) * n_blocks;
+    const size_t off_zero = (off_ids + sizeof(int) * nt + 7) / 8 * 8, off_part = off_zero + sizeof(double) * nt;
+    const size_t off_ratio = off_part + sizeof(double) * nt * TALL_PARTS, off_done = off_ratio + 8 * (size_t)nt;
+    const size_t off_sw = off_done + sizeof(int) * nt, off_items = (off_sw + sizeof(int) * nt + 31) / 32 * 32;
+    const size_t dev_bytes = off_items + sizeof(JacPairItem) * std::max<size_t>(n_items, 1);
+    const size_t pin_bytes = sizeof(JacPairItem) * std::max<size_t>(n_items, 1) + sizeof(int) * (n_blocks + nt);
+    const size_t flag_elems = (size_t)std::max(max_sweeps, 0) + 1;
+    if (dev_bytes > g_js.tall_dev_bytes) {
+        if (g_js.tall_dev) HIP_TRY(hipFree(g_js.tall_dev));
+        g_js.tall_dev = nullptr, g_js.tall_dev_bytes = 0;
+        HIP_TRY(hipMalloc(&g_js.tall_dev, dev_bytes * 2));
+        if (htn_debug_poison()) HIP_TRY(hipMemset(g_js.tall_dev, 0xFF, dev_bytes * 2));
+        g_js.tall_dev_bytes = dev_bytes * 2;
+    }
+    if (pin_bytes > g_js.tall_pin_bytes) {
+        if (g_js.tall_pin) HIP_TRY(hipHostFree(g_js.tall_pin));
+        g_js.tall_pin = nullptr, g_js.tall_pin_bytes = 0;
+        HIP_TRY(hipHostMalloc(&g_js.tall_pin, pin_bytes * 2, hipHostMallocDefault));
+        g_js.tall_pin_bytes = pin_bytes * 2;
+    }
+    if (flag_elems > g_js.tall_flags_elems) {
+        if (g_js.tall_flags) HIP_TRY(hipHostFree(g_js.tall_flags));
+        g_js.tall_flags = nullptr, g_js.tall_flags_elems = 0;
+        HIP_TRY(hipHostMalloc((void**)&g_js.tall_flags, sizeof(int) * flag_elems * 2, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void**)&g_js.tall_flags_dev, g_js.tall_flags, 0));
+        g_js.tall_flags_elems = flag_elems * 2;
+    }
+    char* d = (char*)g_js.tall_dev;
+    int* d_skip = (int*)(d + off_skip);
+    int* d_ids = (int*)(d + off_ids);
+    double* d_zero = (double*)(d + off_zero);
+    double* d_part = (double*)(d + off_part);
+    unsigned long long* d_ratio = (unsigned long long*)(d + off_ratio);
+    int* d_done = (int*)(d + off_done);
+    int* d_sw = (int*)(d + off_sw);
+    JacPairItem* d_items = (JacPairItem*)(d + off_items);
+    JacPairItem* h_items = (JacPairItem*)g_js.tall_pin;
+    int* h_skip = (int*)((char*)g_js.tall_pin + sizeof(JacPairItem) * std::max<size_t>(n_items, 1));
+    int* h_ids = h_skip + n_blocks;
+    volatile int* h_active = (volatile int*)g_js.tall_flags;
+    int* d_active = g_js.tall_flags_dev;
+    std::vector<unsigned char> skip(n_blocks, 0);
+    for (int li = 0; li < nt; ++li) skip[tall[li]] = 1;
+    for (int b = 0; b < n_blocks; ++b) h_skip[b] = skip[b] ? 0 : -1;      // k_jacobi_svd leaves blocks with a slot >= 0
+    for (int li = 0; li < nt; ++li) h_ids[li] = tall[li];
+    {
+        size_t pos = 0;
+        for (auto& rl : rounds)
+            for (auto& it : rl) h_items[pos++] = it;
+    }
+    for (size_t k = 0; k < flag_elems; ++k) h_active[k] = 1;
+    HIP_TRY(hipMemcpyAsync(d_skip, h_skip, sizeof(int) * (n_blocks + nt), hipMemcpyHostToDevice, st));
+    if (n_items) HIP_TRY(hipMemcpyAsync(d_items, h_items, sizeof(JacPairItem) * n_items, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_ratio, 0, 16 * (size_t)nt, st));      // ratio (8 nt) | done (4 nt) | sweeps (4 nt)
+    // everything else first: small blocks, QRCP large blocks (their call returns once they are done)
+    int core_used = 0;
+    if (nt < n_blocks) {
+        if (jacobi_svd_core(G, Vj, S, desc, desc_host, n_blocks, max_m_rest, max_sweeps, tol, info_dev, opts, stream, d_skip,
+                            skip.data()))
+            return 1;
+        if (opts && opts->sweeps_used) core_used = *opts->sweeps_used;
+    }
+    int max_n = 1;
+    for (int li = 0; li < nt; ++li) max_n = std::max(max_n, (int)desc_host[tall[li]].n);
+    hipLaunchKernelGGL(k_jacobi_tall_init, dim3(nt, TALL_PARTS), dim3(256), 0, st, (double2*)G, (double2*)Vj, desc, d_ids, d_part);
+    hipLaunchKernelGGL(k_jacobi_tall_zero, dim3(1), dim3(64), 0, st, (const double*)d_part, d_zero, nt);
+    HIP_TRY(hipGetLastError());
+    // outer sweeps enqueued one ahead of the host's knowledge, bounded by sweeps_hint, as in the pair-visit path
+    const double thr = std::max(tol * tol, 0.1 * tol);
+    auto enqueue_sweep = [&](int sweep) {
+        for (size_t r = 0; r < rounds.size(); ++r)
+            if (!rounds[r].empty())
+                hipLaunchKernelGGL(k_jacobi_tall_visit, dim3((unsigned)rounds[r].size()), dim3(TALL_THREADS), 0, st,
+                                   (double2*)G, (double2*)Vj, desc, d_ids, d_items + r_off[r], d_zero, d_ratio, d_done, tol);
+        hipLaunchKernelGGL(k_jacobi_check, dim3(1), dim3(64), 0, st, d_ratio, d_done, d_sw, nt, thr, d_active + sweep);
+        return hipEventRecord(g_js.ev_sweep[sweep & 1], st);
+    };
+    const int hint = opts && opts->sweeps_hint > 0 ? opts->sweeps_hint : 0;
+    int enq = 0, used = 0;
+    if (max_sweeps > 0) {
+        HIP_TRY(enqueue_sweep(0));
+        enq = 1;
+    }
+    for (int sweep = 0; sweep < max_sweeps; ++sweep) {
+        const bool expect_last = hint > 0 && sweep + 1 >= hint;
+        if (sweep + 1 < max_sweeps && !expect_last && enq == sweep + 1) {
+            HIP_TRY(enqueue_sweep(sweep + 1));
+            ++enq;
+        }
+        HIP_TRY(htn_event_spin(g_js.ev_sweep[sweep & 1]));
+        used = sweep + 1;
+        if (h_active[sweep] == 0) break;
+        if (sweep + 1 < max_sweeps && enq == sweep + 1) {
+            HIP_TRY(enqueue_sweep(sweep + 1));
+            ++enq;
+        }
+    }
+    hipLaunchKernelGGL(k_jacobi_tall_finish, dim3((unsigned)((max_n + 3) / 4), (unsigned)nt), dim3(256), 0, st,
+                       (const double2*)G, S, desc, d_ids, d_sw, d_done, info_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(htn_stream_spin(st));      // the staging blocks are reused by the next call
+    if (opts && opts->sweeps_used) *opts->sweeps_used = std::max(core_used, used);
     return 0;
 }
 

@@ -151,7 +151,11 @@ int htn_lanczos_z(const htn_gemm_launch* stages_host, int32_t n_stages, int32_t 
  * small blocks run beside it on an internal second stream that joins `stream` before the call returns; the call blocks
  * the host until everything has converged, results stay on the device.  Blocks the ring cannot take fall back to the
  * pair-visit block Jacobi of ABI 2 (one launch per tournament round; sweeps_hint bounds its speculative enqueue));
- * max_m_host = max_i max(m_i, pad_i) (<= 512 in this version).
+ * max_m_host = max_i max(m_i, pad_i).  A plain (non-QRCP) block with m_i > 512 ("tall") takes a multi-CU path: the same
+ * pair-visit tournament with its columns streamed from global memory (Gram on MFMA over row chunks, fixed-order sums, U applied
+ * chunk by chunk to X and, with HTN_SVD_ACCUMULATE, to J), one launch per round, sweeps_hint / sweeps_used / max_sweeps as
+ * for the large blocks, no QR preconditioning (more outer sweeps); it runs on `stream` after the other blocks and needs
+ * desc_host (without it m_i > 512 is an error).  Every other block must have max(m_i, pad_i) <= 512.
  * info_dev[i] receives the sweep count (<0: not converged).  A sweep ends the iteration when the largest squared
  * cosine it SAW before rotating was <= max(tol^2, 0.1 tol) (quadratic convergence: it leaves < tol^2 behind). */
 #define HTN_SVD_ACCUMULATE 1      /* flags: also accumulate the rotation J (else Vj is not touched) */
