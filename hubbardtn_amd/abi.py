@@ -96,7 +96,7 @@ assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(Idmr
 
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
-           "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z"]
+           "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z"]
 # entry points shared by libhubbardtn_hip.so and the CPU baseline library (oracle/cpu_backend)
 ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_ctx_set_timing", "htn_comm_unique_id",
                   "htn_ctx_set_comm", "htn_ctx_set_exchange", "htn_mpo_create", "htn_mpo_destroy", "htn_mps_create",
@@ -104,7 +104,8 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_mps_get_theta", "htn_mps_nsites", "htn_mps_bond", "htn_mps_spectrum", "htn_mps_site_size",
                   "htn_mps_get_site", "htn_mps_env_size", "htn_mps_get_env", "htn_mps_env_blocks", "htn_mps_env_bond",
                   "htn_plan_apply_dump", "htn_mps_cache_stats", "htn_balance_tiles",
-                  "htn_idmrg_create", "htn_idmrg_destroy", "htn_idmrg_boundary", "htn_idmrg_step", "htn_idmrg_window"]
+                  "htn_idmrg_create", "htn_idmrg_destroy", "htn_idmrg_boundary", "htn_idmrg_step", "htn_idmrg_window",
+                  "htn_mps_set_orthogonal", "htn_mps_orthogonal_count", "htn_mps_overlap"]
 
 
 class GemmLaunch(C.Structure):
@@ -151,6 +152,9 @@ def load_library(path: str | None = None):
     lib.htn_lanczos_scratch_elems.restype = i64
     lib.htn_lanczos_z.argtypes = [C.POINTER(GemmLaunch), i32, i32, i32, vp, i64, i32, f64, i32, vp, i32,
                                   EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(i32), C.POINTER(f64), C.POINTER(f64), vp]
+    lib.htn_lanczos_orth_z.argtypes = [C.POINTER(GemmLaunch), i32, i32, i32, vp, i64, i32, f64, i32, vp, i32,
+                                       EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(i32), C.POINTER(f64), C.POINTER(f64),
+                                       vp, i32, vp]
     declare_engine(lib)
     for name in EXPORTS + ENGINE_EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
@@ -211,6 +215,9 @@ def declare_engine(lib):
     lib.htn_idmrg_boundary.argtypes = [vp, i32, vp]
     lib.htn_idmrg_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(IdmrgStats)]
     lib.htn_idmrg_window.argtypes = [vp, C.POINTER(vp)]
+    lib.htn_mps_set_orthogonal.argtypes = [vp, C.POINTER(vp), i32]
+    lib.htn_mps_orthogonal_count.argtypes = [vp, C.POINTER(i32)]
+    lib.htn_mps_overlap.argtypes = [vp, vp, C.POINTER(f64)]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

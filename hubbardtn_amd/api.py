@@ -125,10 +125,54 @@ def hamiltonian(simul: Simulation, L: int | None = None):
     return models.hamiltonian(simul, int(L))
 
 
-def initialize_mps(H, P: int, max_dimension: int | None = None, spin: bool = False, Q: int = 1, seed: int = 1234, ops=None):
+def target_sector(sym, nsites: int, P: int = 1, Q: int = 1, charges=None):
+    """total sector (N, j) of a finite chain for the reference's `charges = [parity, spin, dN]` (src:1174, 1185), relative to
+    the filling P/Q: (N0 + dN, 2 spin) in the SU(2) x U(1) mode, (N0 + dN, 2 Sz) with spin=true, (parity, 2 spin) without
+    U(1).  None = the ground-state sector (N0, 0)."""
+    if sym.kind == 2:
+        if charges is None:
+            return (0, 0)
+        parity, j2 = int(charges[0]), 2.0 * float(charges[1])
+        if parity not in (0, 1) or j2 != int(j2) or j2 < 0:
+            raise ValueError("charges = [parity, spin]: parity is 0 or 1 and spin a non-negative multiple of 1/2")
+        if (parity + int(j2)) % 2:
+            raise ValueError("charges: fermion parity and spin do not match (a half-integer spin needs odd parity)")
+        if int(j2) > nsites:
+            raise ValueError(f"charges: a chain of {nsites} sites cannot hold spin {charges[1]}")
+        return (parity, int(j2))
+    if (nsites * P) % Q:
+        raise ValueError("filling P/Q incompatible with the chain length")
+    N0 = nsites * P // Q
+    if charges is None:
+        return (N0, 0)
+    if len(charges) != 3:
+        raise ValueError("charges = [parity, spin, dN]")
+    parity, j2, dN = int(charges[0]), 2.0 * float(charges[1]), int(charges[2])
+    if parity not in (0, 1) or parity != dN % 2:
+        raise ValueError(f"charges: fermion parity {charges[0]} contradicts dN = {dN} (parity = dN mod 2)")
+    if j2 != int(j2) or (sym.su2 and j2 < 0):
+        raise ValueError("charges: spin must be a multiple of 1/2" + (" and non-negative" if sym.su2 else ""))
+    N, j2 = N0 + dN, int(j2)
+    if (N + j2) % 2:
+        raise ValueError(f"charges: spin {charges[1]} with N = {N} electrons (half-integer spin needs odd N, integer spin even N)")
+    if not 0 <= N <= 2 * nsites or abs(j2) > min(N, 2 * nsites - N):
+        raise ValueError(f"charges: a chain of {nsites} sites cannot hold the sector N = {N}, 2S = {j2}")
+    return (N, j2)
+
+
+def initialize_mps(H, P: int, max_dimension: int | None = None, spin: bool = False, Q: int = 1, seed: int = 1234, ops=None,
+                   charges=None):
     """random right-canonical start with per-sector cap `max_dimension` (src:917-959); the symmetry mode (SU(2) x U(1),
     or U(1) x U(1) for `spin=true`) is the Hamiltonian's.  The chemical-potential models use the reference's two-argument
-    form `initialize_mps(operator, max_dimension)` (src:961-991)."""
+    form `initialize_mps(operator, max_dimension)` (src:961-991).  charges = [parity, spin, dN] (finite chains): the total
+    sector of the state, see target_sector; None = the ground-state sector."""
+    if charges is not None and isinstance(H, InfiniteHamiltonian):
+        raise NotImplementedError("initialize_mps: charges need a finite chain")
+    if charges is not None and getattr(H, "sym", None) is models.SU2P:
+        max_dimension = P if max_dimension is None else max_dimension
+        bonds, tensors = mps.random_mps(len(H), target_sector(models.SU2P, len(H), charges=charges), int(max_dimension), seed=seed,
+                                        sym=models.SU2P)
+        return FiniteMPS(_engine.DMRG2(ops or _ops(), H, bonds, tensors), len(H))
     if isinstance(H, InfiniteHamiltonian) and models.symmetry_of(H.simul).kind == 2 or getattr(H, "sym", None) is models.SU2P:
         # (parity 0, S = 0) total sector on a finite chain: an even number of electrons in a singlet
         max_dimension = P if max_dimension is None else max_dimension
@@ -146,9 +190,7 @@ def initialize_mps(H, P: int, max_dimension: int | None = None, spin: bool = Fal
     sym = getattr(H, "sym", models.SU2U1)
     if bool(spin) != (not sym.su2):
         raise ValueError("initialize_mps: `spin` does not match the Hamiltonian's symmetry mode")
-    if (nsites * P) % Q:
-        raise ValueError("filling P/Q incompatible with the chain length")
-    target = (nsites * P // Q, 0)                     # total spin 0 / total Sz 0
+    target = target_sector(sym, nsites, P, Q, charges)  # charges None: total spin 0 / total Sz 0 at filling P/Q
     bonds, tensors = mps.random_mps(nsites, target, max_dimension, seed=seed, sym=sym)
     eng = _engine.DMRG2(ops or _ops(), H, bonds, tensors)
     return FiniteMPS(eng, nsites)
@@ -223,6 +265,112 @@ def produce_groundstate(simul: Simulation, force: bool = False, **kw):
     """src:1145-1166: computes, or loads the result saved under the reference's cache name (storage.produce_or_load)"""
     from . import storage
     return storage.produce_or_load(compute_groundstate, simul, force=force, **kw)
+
+
+def _exc_setup(simul, momenta, nums, charges, L):
+    L = L or simul.kwargs.get("L")
+    if L is None:
+        raise NotImplementedError("excitations of the infinite chain need the quasiparticle ansatz on a uniform MPS "
+                                  "(src:1173-1209), which this library does not have: give a chain length L")
+    if momenta is not None:
+        raise ValueError("an open finite chain has no momentum: momenta must be None")
+    charges = [0, 0.0, 0] if charges is None else list(charges)
+    trivial = not any(float(c) for c in charges)
+    if nums < 1 or nums - (0 if trivial else 1) > 8:
+        raise ValueError("nums: at least 1, and at most 8 states can be attached to a sweep (8 excited states of the ground-state "
+                         "sector, 9 states of any other)")
+    return int(L), charges, trivial
+
+
+def compute_excitations(simul: Simulation, momenta, nums: int, charges=None, L: int | None = None, tol: float = 1e-10,
+                        maxiter: int = 40, chi: int | None = None, seed: int = 4321, verbosity: int = 0, **kw):
+    """finite-chain counterpart of src:1173-1209: the lowest `nums` states of the sector `charges = [parity, spin, dN]` by
+    two-site DMRG in the orthogonal complement of the states found before (engine.DMRG2.set_orthogonal).  -> {"Es", "states",
+    "E0", "charges"}: Es[k] = energy of the k-th state minus the ground-state energy E0 of the sector [0, 0, 0] (the
+    reference measures its Es from its ground state, too); for charges [0, 0, 0] the ground state is the first attached state
+    and Es are the excited states above it.  momenta must be None (no momentum on an open chain)."""
+    L, charges, trivial = _exc_setup(simul, momenta, nums, charges, L)
+    d = produce_groundstate(simul, L=L, chi=chi, tol=min(tol, 1e-6), maxiter=maxiter, **kw)
+    g = d["groundstate"].engine
+    H = d["ham"]
+    E0 = float(g.energy)
+    spin = bool(simul.kwargs.get("spin", False))
+    found, states, Es = ([g] if trivial else []), [], []
+    for k in range(nums):
+        psi = initialize_mps(H, getattr(simul, "P", 1), simul.bond_dim, spin, getattr(simul, "Q", 1), seed=seed + k, ops=g.ops,
+                             charges=charges)
+        eng = psi.engine
+        eng.chi_full, eng.cutoff = g.chi_full, g.cutoff
+        eng.krylovdim = min(g.krylovdim, 31 - len(found))          # row limit of the projected Lanczos step
+        eng.set_orthogonal(found)
+        E_prev = None
+        for it in range(maxiter):
+            E = eng.sweep()
+            if verbosity:
+                print(f"state {k} sweep {it + 1}: E = {E:.12f}")
+            if E_prev is not None and abs(E - E_prev) / L < tol:
+                break
+            E_prev = E
+        found.append(eng)
+        states.append(psi)
+        Es.append(E - E0)
+    return {"Es": np.array(Es), "states": states, "E0": E0, "charges": charges}
+
+
+def produce_excitations(simul: Simulation, momenta, nums: int, force: bool = False, charges=None, L: int | None = None, **kw):
+    """src:1211-1265: compute_excitations, or the entry saved under the reference's prefix rule (storage.excitations_name):
+    the energies as JSON, the states in storage.save_state format"""
+    import json
+    import os
+    from . import storage
+    L, charges, _ = _exc_setup(simul, momenta, nums, charges, L)
+    simul.kwargs.setdefault("L", L)
+    sub, stem = storage.excitations_name(simul, nums, charges)
+    if kw.get("chi"):
+        stem += f"_chi={int(kw['chi'])}"
+    directory = storage.datadir("sims", sub)
+    entry = os.path.join(directory, stem)
+    if os.path.isdir(entry) and not force:
+        meta = json.load(open(os.path.join(entry, "excitations.json")))
+        H = hamiltonian(simul, L)
+        states = []
+        for k in range(nums):
+            bonds, sites = storage.load_state(os.path.join(entry, f"state_{k}"))
+            eng = _engine.DMRG2(_ops(), H, bonds, [s["blocks"] for s in sites], chi_full=meta["chi_full"], cutoff=meta["cutoff"])
+            eng.energy = meta["E0"] + meta["Es"][k]
+            states.append(FiniteMPS(eng, L))
+        return {"Es": np.array(meta["Es"]), "states": states, "E0": meta["E0"], "charges": meta["charges"]}
+    res = compute_excitations(simul, None, nums, charges=charges, L=L, **kw)
+    try:
+        os.makedirs(directory, exist_ok=True)
+        if os.path.isdir(entry):
+            import shutil
+            shutil.rmtree(entry)
+        os.makedirs(entry)
+        for k, psi in enumerate(res["states"]):
+            storage.save_state(psi, entry, f"state_{k}")
+        e0 = res["states"][0].engine
+        with open(os.path.join(entry, "excitations.json"), "w") as f:
+            json.dump({"Es": [float(x) for x in res["Es"]], "E0": res["E0"], "charges": [float(c) for c in res["charges"]],
+                       "chi_full": e0.chi_full, "cutoff": e0.cutoff}, f)
+    except OSError:
+        pass
+    return res
+
+
+def produce_bandgap(simul: Simulation, L: int | None = None, force: bool = False, **kw):
+    """src:1267-1299 on an open chain: the charge gap E0(N+1, 1/2) + E0(N-1, 1/2) - 2 E0(N, 0) as Es_hole[0] + Es_elec[0]
+    with charges [1, 1/2, -1] and [1, 1/2, +1] (src:1284-1285)"""
+    if bool(simul.kwargs.get("spin", False)):
+        raise NotImplementedError("Band gap for spin systems not implemented.")
+    hole = produce_excitations(simul, None, 1, force=force, charges=[1, 0.5, -1], L=L, **kw)
+    elec = produce_excitations(simul, None, 1, force=force, charges=[1, 0.5, 1], L=L, **kw)
+    return float(hole["Es"][0] + elec["Es"][0])
+
+
+def spin_gap(simul: Simulation, L: int | None = None, force: bool = False, **kw):
+    """E0(N, S = 1) - E0(N, 0): the lowest state of charges [0, 1, 0] above the ground state"""
+    return float(produce_excitations(simul, None, 1, force=force, charges=[0, 1.0, 0], L=L, **kw)["Es"][0])
 
 
 def expectation_value(psi: FiniteMPS, H):

@@ -229,18 +229,60 @@ struct HipBackend : htn::Backend {
     int lanczos(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim,
                 double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, double* eig, int* n_matvec,
                 double* residual, double* matvec_ms) override {
-        const int64_t need = htn_lanczos_scratch_elems(krylovdim);
+        if (ensure_lan_scratch(htn_lanczos_scratch_elems(krylovdim))) return 1;
+        int32_t nmv = 0;
+        const int rc = htn_lanczos_z(stages, n_stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, lan_scratch, zero_y,
+                                     exchange, user, eig, &nmv, residual, matvec_ms, st);
+        *n_matvec = nmv;
+        return rc;
+    }
+    int ensure_lan_scratch(int64_t need) {
         if (need > lan_scratch_elems) {
             if (lan_scratch) HIP_TRY(hipFree(lan_scratch));
             HIP_TRY(hipMalloc(&lan_scratch, sizeof(double2) * need));
             if (htn_debug_poison()) HIP_TRY(hipMemsetAsync(lan_scratch, 0xFF, sizeof(double2) * need, st));
             lan_scratch_elems = need;
         }
+        return 0;
+    }
+    int lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim,
+                     double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, const void* Q, int n_frozen,
+                     double* eig, int* n_matvec, double* residual, double* matvec_ms) override {
+        if (ensure_lan_scratch(htn_lanczos_scratch_elems(krylovdim + n_frozen))) return 1;
         int32_t nmv = 0;
-        const int rc = htn_lanczos_z(stages, n_stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, lan_scratch, zero_y,
-                                     exchange, user, eig, &nmv, residual, matvec_ms, st);
+        const int rc = htn_lanczos_orth_z(stages, n_stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, lan_scratch, zero_y,
+                                          exchange, user, eig, &nmv, residual, matvec_ms, Q, n_frozen, st);
         *n_matvec = nmv;
         return rc;
+    }
+    // Gram-Schmidt of the projector rows on the device (htn_dots_z / htn_axpys_z, two passes per row); the host sees two
+    // squared norms per row and decides whether the row stays
+    int orthonormalise_rows(void* Pv, int64_t n, int nvec, double drop_tol, int* kept) override {
+        if (nvec > 32) return htn::set_error("orthonormalise_rows: more than 32 rows");
+        if (ensure_lan_scratch(htn_dots_scratch_elems(32) + 64)) return 1;
+        double2* P = (double2*)Pv;
+        double2* part = (double2*)lan_scratch;
+        double2* coef = part + htn_dots_scratch_elems(32);       // [32] coefficients, then n0, n1
+        double2* nrm = coef + 32;
+        int k = 0;
+        for (int r = 0; r < nvec; ++r) {
+            double2* dst = P + (int64_t)k * n;
+            if (r != k) HIP_TRY(hipMemcpyAsync(dst, P + (int64_t)r * n, sizeof(double2) * n, hipMemcpyDeviceToDevice, st));
+            if (htn_dots_z(dst, n, 1, dst, n, nrm, part, st)) return 1;
+            for (int pass = 0; pass < 2 && k > 0; ++pass) {
+                if (htn_dots_z(P, n, k, dst, n, coef, part, st)) return 1;
+                if (htn_axpys_z(dst, P, n, k, coef, -1.0, n, st)) return 1;
+            }
+            if (htn_dots_z(dst, n, 1, dst, n, nrm + 1, part, st)) return 1;
+            double h[4];
+            if (download(h, nrm, sizeof(h))) return 1;
+            const double n0 = h[0], n1 = h[2];
+            if (!(n0 > 0.0) || !(n1 > drop_tol * drop_tol * n0)) continue;
+            if (htn_scale_inv_sqrt_z(dst, dst, nrm + 1, n, st)) return 1;
+            ++k;
+        }
+        *kept = k;
+        return 0;
     }
     int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host, int n_blocks,
                    int max_m, int max_sweeps, double tol, int32_t* info_dev, const htn_svd_opts* opts) override {

@@ -245,6 +245,39 @@ void plan_left_env(const Mpo& mpo, const EnvLayout& Ll, const SiteLayout& lay, c
 void plan_right_env(const Mpo& mpo, const EnvLayout& Rl, const SiteLayout& lay, const MpoSite& W, const EnvLayout& Rnew,
                     EnvPlan& out);
 
+// ---- overlap environments <psi|phi> of two states on the same chain (orthogonalised DMRG, htn_mps_overlap) ----------
+// A scalar transfer has no MPO level and is diagonal in the sector label: per sector c common to both bond tables one dense
+// [rows.dim(c) x cols.dim(c)] block.  Left environments are stored [bra psi x ket phi], right ones [ket phi x bra psi].
+// Recoupling factor: 1.  In the tilde normalisation the product of the STORED blocks along a path of sectors equals
+// sqrt(2J+1) x the product of the bare (left-coupled) reduced blocks whatever the gauge -- left isometries carry 1, the centre
+// sqrt(q_r), right tensors sqrt(q_r / q_l), which telescopes to the total sector's q_J -- and paths through different sectors
+// or site multiplets are orthogonal, so <psi|phi> is the plain sector-diagonal transfer of the stored blocks.
+struct OvlLayout {
+    BondP rows, cols;
+    std::vector<Sec> secs;
+    std::vector<int64_t> off;
+    std::vector<int32_t> m, n;
+    std::unordered_map<uint64_t, int> index;
+    int64_t size = 0;
+    int find(Sec s) const {
+        auto it = index.find(skey(s));
+        return it == index.end() ? -1 : it->second;
+    }
+};
+typedef std::shared_ptr<const OvlLayout> OvlLayoutP;
+OvlLayoutP build_ovl_layout(BondP rows, BondP cols);
+struct OvlPlan {
+    Tasks t1, t2;                // stage 1 -> BUF_Z, stage 2 -> BUF_Y
+    int64_t zsize = 0;
+};
+// one site to the right: BUF_L = O_L[bra x ket] of the site's left bond, BUF_S1 = bra site, BUF_S2 = ket site (any layout kind)
+void plan_ovl_left(const OvlLayout& Ol, const SiteLayout& bra, const SiteLayout& ket, const OvlLayout& Onew, OvlPlan& out);
+// one site to the left: BUF_R = O_R[ket x bra] of the site's right bond
+void plan_ovl_right(const OvlLayout& Or, const SiteLayout& bra, const SiteLayout& ket, const OvlLayout& Onew, OvlPlan& out);
+// p = O_L . (K1 K2) . O_R in the bra's theta layout tl: BUF_S1 / BUF_S2 = the ket's two site tensors; <p, theta> = <phi|psi(theta)>
+void plan_ovl_project(const OvlLayout& Ol, const OvlLayout& Or, const SiteLayout& k1, const SiteLayout& k2, const ThetaLayout& tl,
+                      OvlPlan& out);
+
 struct SvdPlan {
     std::vector<htn_svd_block> desc;
     std::vector<htn_copy_item> stage;
@@ -286,6 +319,16 @@ struct Backend {
     virtual int lanczos(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n,
                         int krylovdim, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
                         double* eig, int* n_matvec, double* residual, double* matvec_ms) = 0;
+    // Lowest eigenpair of P H P, P = 1 - Q Q^H, for n_frozen orthonormal device rows Q of length n (start vector projected
+    // first; V as for lanczos).  NOT pure: the default (htn_engine.cpp) is a plain host statement of the method -- vectors
+    // downloaded, H applied through grouped_gemm, full reorthogonalisation against Q and the basis in two passes, the stopping
+    // rule of lanczos -- which the CPU baseline library inherits; the HIP backend overrides it with htn_lanczos_orth_z.
+    virtual int lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n,
+                             int krylovdim, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
+                             const void* Q, int n_frozen, double* eig, int* n_matvec, double* residual, double* matvec_ms);
+    // Gram-Schmidt (two passes) of the nvec device rows P in place, in order; a row whose remainder falls below drop_tol x its
+    // norm is dropped and the rows behind it move up.  -> *kept orthonormal rows.  Default: on the host.
+    virtual int orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept);
     virtual int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host,
                            int n_blocks, int max_m, int max_sweeps, double tol, int32_t* info_dev,
                            const htn_svd_opts* opts) = 0;

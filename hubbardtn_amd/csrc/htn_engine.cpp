@@ -25,6 +25,174 @@ Backend* make_backend(int backend, int device, void* stream);       // one per l
 }
 using namespace htn;
 
+// ---- host statements of the two Backend methods that are not pure (htn_core.h) ---------------------------------------
+namespace {
+// lowest eigenpair of the symmetric tridiagonal (alpha, beta): bisection on the Sturm count, then inverse iteration
+void tridiag_lowest_host(const std::vector<double>& alpha, const std::vector<double>& beta, double* eig, std::vector<double>& vec) {
+    const int k = (int)alpha.size();
+    auto count = [&](double x) {
+        int cnt = 0;
+        double d = 1.0;
+        for (int i = 0; i < k; ++i) {
+            d = (alpha[i] - x) - (i ? beta[i - 1] * beta[i - 1] / d : 0.0);
+            if (d == 0.0) d = 1e-300;
+            if (d < 0.0) ++cnt;
+        }
+        return cnt;
+    };
+    double lo = alpha[0], hi = alpha[0];
+    for (int i = 0; i < k; ++i) {
+        const double r = (i ? fabs(beta[i - 1]) : 0.0) + (i + 1 < k ? fabs(beta[i]) : 0.0);
+        lo = fmin(lo, alpha[i] - r);
+        hi = fmax(hi, alpha[i] + r);
+    }
+    const double scale = fmax(fabs(lo), fabs(hi)) + 1e-300;
+    hi += 1e-12 * scale;
+    for (int it = 0; it < 200 && hi - lo > 4e-16 * scale; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (count(mid) >= 1) hi = mid;
+        else lo = mid;
+    }
+    const double lam = 0.5 * (lo + hi);
+    *eig = lam;
+    vec.assign(k, 1.0);
+    if (k == 1) return;
+    const double mu = lam - 1e-10 * scale;
+    std::vector<double> d(k), l(k), z(k);
+    d[0] = alpha[0] - mu;
+    for (int i = 1; i < k; ++i) {
+        l[i] = beta[i - 1] / d[i - 1];
+        d[i] = (alpha[i] - mu) - l[i] * beta[i - 1];
+        if (d[i] == 0.0) d[i] = 1e-300;
+    }
+    for (int i = 0; i < k; ++i) vec[i] = (i & 1) ? -0.7 : 1.0;
+    for (int iter = 0; iter < 4; ++iter) {
+        z[0] = vec[0];
+        for (int i = 1; i < k; ++i) z[i] = vec[i] - l[i] * z[i - 1];
+        z[k - 1] /= d[k - 1];
+        for (int i = k - 2; i >= 0; --i) z[i] = z[i] / d[i] - l[i + 1] * z[i + 1];
+        double nn = 0.0;
+        for (int i = 0; i < k; ++i) nn += z[i] * z[i];
+        nn = 1.0 / sqrt(nn);
+        for (int i = 0; i < k; ++i) vec[i] = z[i] * nn;
+    }
+    if (vec[0] < 0.0)
+        for (int i = 0; i < k; ++i) vec[i] = -vec[i];
+}
+cplx hdot(const cplx* a, const cplx* b, int64_t n) {
+    cplx s = 0.0;
+    for (int64_t e = 0; e < n; ++e) s += std::conj(a[e]) * b[e];
+    return s;
+}
+// w -= sum_r rows[r] <rows[r], w>, twice; returns the sum of <rows[pick], w> over both passes
+double hproject(const std::vector<const cplx*>& rows, cplx* w, int64_t n, int pick) {
+    double got = 0.0;
+    std::vector<cplx> c(rows.size());
+    for (int pass = 0; pass < 2; ++pass) {
+        for (size_t r = 0; r < rows.size(); ++r) c[r] = hdot(rows[r], w, n);
+        if (pick >= 0) got += c[(size_t)pick].real();
+        for (size_t r = 0; r < rows.size(); ++r)
+            for (int64_t e = 0; e < n; ++e) w[e] -= c[r] * rows[r][e];
+    }
+    return got;
+}
+}  // namespace
+
+int Backend::lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* Vv, int64_t n, int kd, double tol,
+                          int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, const void* Qv, int nf, double* eig,
+                          int* n_matvec, double* residual, double* matvec_ms) {
+    if (kd < 2 || nf < 0) return set_error("lanczos_orth: krylovdim >= 2 and n_frozen >= 0 required");
+    cplx* Vd = (cplx*)Vv;
+    const size_t bytes = sizeof(cplx) * (size_t)n;
+    std::vector<cplx> Q((size_t)nf * n), B((size_t)(kd + 1) * n), x((size_t)n);
+    if (nf && download(Q.data(), Qv, bytes * nf)) return 1;
+    if (download(B.data(), Vd, bytes)) return 1;
+    auto matvec = [&](const cplx* v, cplx* w) -> int {        // through device rows kd (x) and kd + 1 (y) of the caller's V
+        cplx *xd = Vd + (int64_t)kd * n, *yd = Vd + (int64_t)(kd + 1) * n;
+        if (upload(xd, v, bytes)) return 1;
+        if (zero_y && zero(yd, bytes)) return 1;
+        for (int s = 0; s < n_stages; ++s) {
+            const void* bufs[HTN_MAX_BUFS];
+            for (int b = 0; b < HTN_MAX_BUFS; ++b) bufs[b] = stages[s].bufs[b];
+            bufs[x_slot] = xd;
+            bufs[y_slot] = yd;
+            if (stages[s].n_tiles > 0 && grouped_gemm(bufs, stages[s].tiles, stages[s].n_tiles, stages[s].segs)) return 1;
+        }
+        if (exchange && exchange(yd, n, user)) return set_error("lanczos_orth: the exchange hook reported a failure");
+        return download(w, yd, bytes);
+    };
+    auto normalise = [&](cplx* v) {
+        const double nn = hdot(v, v, n).real();
+        const double s = nn > 0.0 ? 1.0 / sqrt(nn) : 0.0;
+        for (int64_t e = 0; e < n; ++e) v[e] *= s;
+        return nn;
+    };
+    std::vector<const cplx*> qrows;
+    for (int r = 0; r < nf; ++r) qrows.push_back(Q.data() + (int64_t)r * n);
+    hproject(qrows, B.data(), n, -1);
+    if (!(normalise(B.data()) > 0.0)) return set_error("lanczos_orth: the start vector lies in the span of the frozen rows");
+    int nmv = 0;
+    double theta = 0.0, res = 0.0, beta = 0.0, amax = 0.0;
+    std::vector<double> y;
+    for (int restart = 0; restart <= max_restart; ++restart) {
+        std::vector<double> alphas, betas;
+        for (int j = 0; j < kd; ++j) {
+            cplx* w = B.data() + (int64_t)(j + 1) * n;
+            if (matvec(B.data() + (int64_t)j * n, w)) return 1;
+            ++nmv;
+            std::vector<const cplx*> rows = qrows;
+            for (int r = 0; r <= j; ++r) rows.push_back(B.data() + (int64_t)r * n);
+            const double alpha = hproject(rows, w, n, nf + j);
+            beta = sqrt(hdot(w, w, n).real());
+            if (!(alpha == alpha) || !(beta == beta)) return set_error("lanczos_orth: NaN in the tridiagonal coefficients");
+            alphas.push_back(alpha);
+            tridiag_lowest_host(alphas, betas, &theta, y);
+            res = fabs(beta * y.back());
+            amax = std::max(amax, std::max(fabs(alpha), beta));
+            if (res < tol || beta < 1e-14 * std::max(amax, 1e-300) || j == kd - 1) break;
+            betas.push_back(beta);
+            const double inv = 1.0 / beta;
+            for (int64_t e = 0; e < n; ++e) w[e] *= inv;
+        }
+        const int k = (int)y.size();
+        std::fill(x.begin(), x.end(), cplx(0.0, 0.0));
+        for (int r = 0; r < k; ++r)
+            for (int64_t e = 0; e < n; ++e) x[e] += y[r] * B[(size_t)r * n + e];
+        hproject(qrows, x.data(), n, -1);
+        normalise(x.data());
+        memcpy((void*)B.data(), x.data(), bytes);
+        if (res < tol || beta < 1e-14 * std::max(amax, 1e-300)) break;
+    }
+    if (upload(Vd, B.data(), bytes) || sync()) return 1;
+    *eig = theta;
+    *n_matvec = nmv;
+    *residual = res;
+    if (matvec_ms) *matvec_ms = 0.0;
+    return 0;
+}
+
+int Backend::orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept) {
+    std::vector<cplx> h((size_t)nvec * n);
+    if (nvec && download(h.data(), P, sizeof(cplx) * h.size())) return 1;
+    std::vector<const cplx*> rows;
+    int k = 0;
+    for (int r = 0; r < nvec; ++r) {
+        cplx* dst = h.data() + (int64_t)k * n;
+        if (r != k) memcpy((void*)dst, h.data() + (int64_t)r * n, sizeof(cplx) * (size_t)n);
+        const double n0 = hdot(dst, dst, n).real();
+        hproject(rows, dst, n, -1);
+        const double n1 = hdot(dst, dst, n).real();
+        if (!(n0 > 0.0) || !(n1 > drop_tol * drop_tol * n0)) continue;
+        const double sc = 1.0 / sqrt(n1);
+        for (int64_t e = 0; e < n; ++e) dst[e] *= sc;
+        rows.push_back(dst);
+        ++k;
+    }
+    if (k && (upload(P, h.data(), sizeof(cplx) * (size_t)k * n) || sync())) return 1;
+    *kept = k;
+    return 0;
+}
+
 // Handles are reference counted: an htn_mps keeps its context and its MPO alive, so destroying the handles in any order
 // (garbage-collected host languages do exactly that) is safe; the last release frees the object.
 struct htn_ctx {
@@ -114,6 +282,16 @@ struct Spectrum {
     std::vector<Sec> secs;
     std::vector<std::vector<double>> vals;
 };
+struct OvlC {                      // compiled overlap transfer / projection (plan_ovl_*)
+    OvlLayoutP lay;                // layout of the result (transfers)
+    DevTasks d1, d2;
+    int64_t zsize = 0;
+};
+struct OrthState {                 // one attached state phi: overlap environments <psi|phi> per bond, carried along the sweep
+    htn_mps* phi = nullptr;
+    std::vector<OvlLayoutP> Llay, Rlay;
+    std::vector<DView> Lbuf, Rbuf;
+};
 
 }  // namespace
 
@@ -136,6 +314,8 @@ struct htn_mps {
     std::map<int, std::pair<std::pair<int, double>, double>> cut_hint;      // bond -> ((chi, cutoff), smallest kept value)
     std::map<int, int> sweeps_hint;     // bond -> outer Jacobi sweeps its large blocks needed last time (htn_svd_opts.sweeps_hint)
     std::vector<int32_t> idx_host;
+    std::vector<OrthState> orth;        // htn_mps_set_orthogonal: the sweep stays in the orthogonal complement of these states
+    int orth_dropped = 0;               // projector vectors dropped as numerically dependent in the last bond update
 
     template <class T, class F>
     std::shared_ptr<T> cached(const std::string& key, F build) {
@@ -219,6 +399,13 @@ struct htn_mps {
 
     int left_env(int i);
     int right_env(int i);
+    // overlap transfers with `ket` as the ket state (this = bra): in -> out across site i
+    int ovl_left(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);
+    int ovl_right(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);
+    int ovl_boundary(const htn_mps* ket, int b, OvlLayoutP* outl, DView* out);
+    int ovl_project(const OrthState& o, int i, const ThetaLayout& tl, cplx* dst);
+    int orth_attach(htn_mps* const* others, int n);
+    void orth_detach();
     std::shared_ptr<ApplyC> make_apply(int i, const ThetaLayout& tl);
     int theta_into(int i, const ThetaLayout& tl, cplx* dst);
     int update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
@@ -272,6 +459,117 @@ int htn_mps::right_env(int i) {
     if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, out.ptr()}})) return 1;
     Rlay[i] = c->lay;
     Rbuf[i] = out;
+    return 0;
+}
+
+// ---- overlap environments (orthogonalised DMRG, htn_mps_overlap) ------------------------------------------------------
+int htn_mps::ovl_boundary(const htn_mps* ket, int b, OvlLayoutP* outl, DView* out) {
+    OvlLayoutP lay = b == 0 ? build_ovl_layout(bonds[0], ket->bonds[0]) : build_ovl_layout(ket->bonds[L], bonds[L]);
+    if (lay->size != 1) return set_error("overlap: the end bonds of the two states are not one common sector of dimension 1");
+    DView v = zalloc(1, false);
+    const cplx one(1.0, 0.0);
+    if (!v.base || be->upload(v.ptr(), &one, sizeof(one))) return set_error("overlap: device allocation failed");
+    *outl = lay;
+    *out = v;
+    return 0;
+}
+
+int htn_mps::ovl_left(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out) {
+    const SiteLayout &lb = *site_lay[i], &lk = *ket->site_lay[i];
+    auto c = cached<OvlC>(std::string("ovlL") + lb.kind + lk.kind + bonds[i]->key + "|" + bonds[i + 1]->key + "|" + ket->bonds[i]->key + "|" +
+                              ket->bonds[i + 1]->key,
+                          [&]() -> std::shared_ptr<OvlC> {
+                              auto e = std::make_shared<OvlC>();
+                              e->lay = build_ovl_layout(bonds[i + 1], ket->bonds[i + 1]);
+                              OvlPlan p;
+                              plan_ovl_left(*inl, lb, lk, *e->lay, p);
+                              if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
+                              e->zsize = p.zsize;
+                              return e;
+                          });
+    if (!c) return 1;
+    DView z = zalloc(c->zsize, false), o = zalloc(c->lay->size, true);
+    if (!z.base || !o.base) return set_error("device allocation failed (overlap environment)");
+    if (gemm(c->d1, {{BUF_L, in.ptr()}, {BUF_S2, ket->site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
+    *outl = c->lay;
+    *out = o;
+    return 0;
+}
+
+int htn_mps::ovl_right(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out) {
+    const SiteLayout &lb = *site_lay[i], &lk = *ket->site_lay[i];
+    auto c = cached<OvlC>(std::string("ovlR") + lb.kind + lk.kind + bonds[i]->key + "|" + bonds[i + 1]->key + "|" + ket->bonds[i]->key + "|" +
+                              ket->bonds[i + 1]->key,
+                          [&]() -> std::shared_ptr<OvlC> {
+                              auto e = std::make_shared<OvlC>();
+                              e->lay = build_ovl_layout(ket->bonds[i], bonds[i]);
+                              OvlPlan p;
+                              plan_ovl_right(*inl, lb, lk, *e->lay, p);
+                              if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
+                              e->zsize = p.zsize;
+                              return e;
+                          });
+    if (!c) return 1;
+    DView z = zalloc(c->zsize, false), o = zalloc(c->lay->size, true);
+    if (!z.base || !o.base) return set_error("device allocation failed (overlap environment)");
+    if (gemm(c->d1, {{BUF_R, in.ptr()}, {BUF_S2, ket->site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
+    *outl = c->lay;
+    *out = o;
+    return 0;
+}
+
+// row of the projector: <phi| carried into the bases of this state's bond (i, i+1), in its theta layout
+int htn_mps::ovl_project(const OrthState& os, int i, const ThetaLayout& tl, cplx* dst) {
+    const htn_mps* ket = os.phi;
+    const SiteLayout &k1 = *ket->site_lay[i], &k2 = *ket->site_lay[i + 1];
+    auto c = cached<OvlC>(std::string("ovlP") + k1.kind + k2.kind + bonds[i]->key + "|" + bonds[i + 2]->key + "|" + ket->bonds[i]->key + "|" +
+                              ket->bonds[i + 1]->key + "|" + ket->bonds[i + 2]->key,
+                          [&]() -> std::shared_ptr<OvlC> {
+                              auto e = std::make_shared<OvlC>();
+                              OvlPlan p;
+                              plan_ovl_project(*os.Llay[i], *os.Rlay[i + 2], k1, k2, tl, p);
+                              if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
+                              e->zsize = p.zsize;
+                              return e;
+                          });
+    if (!c) return 1;
+    DView z = zalloc(c->zsize, false);
+    if (!z.base) return set_error("device allocation failed (projector row)");
+    if (gemm(c->d1, {{BUF_L, os.Lbuf[i].ptr()}, {BUF_R, os.Rbuf[i + 2].ptr()}, {BUF_S1, ket->site_buf[i].ptr()},
+                     {BUF_S2, ket->site_buf[i + 1].ptr()}, {BUF_Z, z.ptr()}}))
+        return 1;
+    return gemm(c->d2, {{BUF_Z, z.ptr()}, {BUF_Y, dst}});
+}
+
+void htn_mps::orth_detach() {
+    for (auto& os : orth) htn_mps_destroy(os.phi);
+    orth.clear();
+    orth_dropped = 0;
+}
+
+// Overlap environments of every bond from the tensors as they are now (a scalar transfer needs no particular gauge); the
+// sweep then keeps them current exactly as it keeps the H environments.  The attached states must not change while attached.
+int htn_mps::orth_attach(htn_mps* const* others, int n) {
+    std::vector<OrthState> fresh((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        OrthState& os = fresh[k];
+        os.phi = others[k];
+        os.Llay.resize(L + 1);
+        os.Rlay.resize(L + 1);
+        os.Lbuf.resize(L + 1);
+        os.Rbuf.resize(L + 1);
+        if (ovl_boundary(os.phi, 0, &os.Llay[0], &os.Lbuf[0]) || ovl_boundary(os.phi, L, &os.Rlay[L], &os.Rbuf[L])) return 1;
+        for (int i = 0; i < L; ++i)
+            if (ovl_left(os.phi, i, os.Llay[i], os.Lbuf[i], &os.Llay[i + 1], &os.Lbuf[i + 1])) return 1;
+        for (int i = L - 1; i >= 0; --i)
+            if (ovl_right(os.phi, i, os.Rlay[i + 1], os.Rbuf[i + 1], &os.Rlay[i], &os.Rbuf[i])) return 1;
+    }
+    if (be->sync()) return 1;
+    for (int k = 0; k < n; ++k) ++others[k]->refs;
+    orth_detach();
+    orth.swap(fresh);
     return 0;
 }
 
@@ -359,8 +657,27 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
     double E = 0.0, res = 0.0, mv_ms = 0.0;
     int nmv = 0;
     const bool shard = ctx->shard;
-    if (be->lanczos(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, shard ? 1 : 0,
-                    shard ? exchange_tramp : nullptr, ctx, &E, &nmv, &res, be->timing ? &mv_ms : nullptr))
+    int n_frozen = 0;
+    DView Qb;
+    if (!orth.empty() && optimise) {
+        // orthogonalised update: p_k = <phi_k| carried into this bond's bases, one row each; Gram-Schmidt (rows that depend on
+        // the ones before them are dropped); then the lowest eigenpair of H_eff inside the complement of those rows
+        const int na = (int)orth.size();
+        if (kd + na > 31)
+            return set_error("htn_bond_update: krylovdim + attached states = %d + %d > 31 (row limit of the projected Lanczos step)", kd, na);
+        Qb = zalloc((int64_t)na * n, false);
+        if (!Qb.base) return set_error("device allocation of the projector rows failed");
+        for (int k = 0; k < na; ++k)
+            if (ovl_project(orth[k], i, tl, Qb.ptr() + (int64_t)k * n)) return 1;
+        if (be->orthonormalise_rows(Qb.ptr(), n, na, 1e-12, &n_frozen)) return 1;
+        orth_dropped = na - n_frozen;
+    }
+    if (n_frozen > 0) {
+        if (be->lanczos_orth(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, o.lanczos_tol, o.maxrestart, shard ? 1 : 0,
+                             shard ? exchange_tramp : nullptr, ctx, Qb.ptr(), n_frozen, &E, &nmv, &res, be->timing ? &mv_ms : nullptr))
+            return 1;
+    } else if (be->lanczos(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, shard ? 1 : 0,
+                           shard ? exchange_tramp : nullptr, ctx, &E, &nmv, &res, be->timing ? &mv_ms : nullptr))
         return 1;
     if (o.profile) be->sync();
     const double t_lan = now() - t0 - t_plan;
@@ -570,6 +887,10 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
     if (o.profile) be->sync();
     const double t_svd = now() - t0 - t_plan - t_lan;
     if (right ? left_env(i) : right_env(i + 1)) return 1;
+    for (auto& os : orth)          // the overlap environments move with the H environment (non-optimising moves too)
+        if (right ? ovl_left(os.phi, i, os.Llay[i], os.Lbuf[i], &os.Llay[i + 1], &os.Lbuf[i + 1])
+                  : ovl_right(os.phi, i + 1, os.Rlay[i + 2], os.Rbuf[i + 2], &os.Rlay[i + 1], &os.Rbuf[i + 1]))
+            return 1;
     if (o.profile) be->sync();
     const double t_env = now() - t0 - t_plan - t_lan - t_svd;
     energy = E;
@@ -1391,6 +1712,7 @@ void htn_mps_destroy(htn_mps* mps) {
     htn_ctx* c = mps->ctx;
     htn_mpo* m = mps->mpo_handle;
     if (mps->be) (void)mps->be->activate();
+    mps->orth_detach();      // references to attached states
     delete mps;              // device buffers go back to the backend's pool first ...
     mpo_release(m);          // ... then the references that kept the backend alive
     ctx_release(c);
@@ -1422,6 +1744,62 @@ int htn_bond_update(htn_mps* mps, int32_t i, int32_t direction, int32_t placemen
 int htn_dmrg2_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* stats, double* energy) {
     if (mps->be->activate()) return 1;
     return mps->sweep(norm_opts(opts), stats, energy);
+}
+
+int htn_mps_set_orthogonal(htn_mps* mps, const htn_mps* const* others, int32_t n) {
+    if (!mps || n < 0 || (n > 0 && !others)) return set_error("htn_mps_set_orthogonal: bad arguments");
+    if (n > 8) return set_error("htn_mps_set_orthogonal: at most 8 attached states (%d given)", n);
+    if (mps->be->activate()) return 1;
+    if (n == 0) {
+        mps->orth_detach();
+        return 0;
+    }
+    if (mps->ctx->world > 1) return set_error("htn_mps_set_orthogonal: not available on a context with a communicator");
+    std::vector<htn_mps*> list;
+    for (int k = 0; k < n; ++k) {
+        htn_mps* o = const_cast<htn_mps*>(others[k]);
+        if (!o || o == mps) return set_error("htn_mps_set_orthogonal: state %d is NULL or the state itself", k);
+        if (o->ctx != mps->ctx) return set_error("htn_mps_set_orthogonal: state %d lives in a different context", k);
+        if (o->L != mps->L) return set_error("htn_mps_set_orthogonal: state %d has %d sites, this state %d", k, o->L, mps->L);
+        const Sym &a = mps->mpo->sym, &b = o->mpo->sym;
+        bool same = a.kind == b.kind && a.n_site == b.n_site;
+        for (int q = 0; same && q < a.n_site; ++q) same = a.site[q] == b.site[q];
+        if (!same) return set_error("htn_mps_set_orthogonal: state %d has a different symmetry", k);
+        if (o->bonds[0]->key != mps->bonds[0]->key || o->bonds[o->L]->key != mps->bonds[mps->L]->key)
+            return set_error("htn_mps_set_orthogonal: state %d is in a different total sector", k);
+        if (mps->bonds[0]->dim_full(a) != 1 || mps->bonds[mps->L]->secs.size() != 1 || mps->bonds[mps->L]->dims[0] != 1)
+            return set_error("htn_mps_set_orthogonal: the end bonds must be single sectors of dimension 1 (a finite chain)");
+        list.push_back(o);
+    }
+    return mps->orth_attach(list.data(), n);
+}
+int32_t htn_mps_orthogonal_count(const htn_mps* mps, int32_t* dropped_host) {
+    if (dropped_host) *dropped_host = mps->orth_dropped;
+    return (int32_t)mps->orth.size();
+}
+int htn_mps_overlap(htn_mps* a, const htn_mps* b, double* out_host) {
+    if (!a || !b || !out_host) return set_error("htn_mps_overlap: bad arguments");
+    if (a->ctx != b->ctx) return set_error("htn_mps_overlap: the states live in different contexts");
+    if (a->L != b->L) return set_error("htn_mps_overlap: %d and %d sites", a->L, b->L);
+    if (a->be->activate()) return 1;
+    out_host[0] = out_host[1] = 0.0;
+    if (a->bonds[0]->key != b->bonds[0]->key || a->bonds[a->L]->key != b->bonds[b->L]->key) return 0;      // different total sectors
+    OvlLayoutP lay;
+    DView buf;
+    if (a->ovl_boundary(b, 0, &lay, &buf)) return 1;
+    for (int i = 0; i < a->L; ++i) {
+        OvlLayoutP nl;
+        DView nb;
+        if (a->ovl_left(b, i, lay, buf, &nl, &nb)) return 1;
+        lay = nl;
+        buf = nb;
+    }
+    if (lay->size != 1) return set_error("htn_mps_overlap: the right end bonds are not one sector of dimension 1");
+    cplx v;
+    if (a->be->download(&v, buf.ptr(), sizeof(v))) return 1;
+    out_host[0] = v.real();
+    out_host[1] = v.imag();
+    return 0;
 }
 
 int64_t htn_mps_theta_size(htn_mps* mps, int32_t i) {

@@ -43,6 +43,16 @@
     } while (0)
 static inline int64_t dot_slice(int64_t n) { return (n + DOT_BLOCKS - 1) / DOT_BLOCKS; }
 
+// FROZEN ROWS (htn_lanczos_orth_z).  The three kernels of a Lanczos step take a second base pointer: with FZ the rows of a
+// pass are the nf frozen rows Q[0..nf) FOLLOWED by the Krylov rows (row i >= nf is V[i - nf]).  FZ is a template parameter, so
+// the instantiations htn_lanczos_z uses (FZ = false) never look at Q / nf: their code and register counts are those of the
+// two-pointer-free kernels.
+template <bool FZ>
+__device__ __forceinline__ const double2* lan_row(const double2* V, const double2* Q, int64_t ldv, int nf, int i) {
+    if (FZ && i < nf) return Q + (int64_t)i * ldv;
+    return V + (int64_t)(FZ ? i - nf : i) * ldv;
+}
+
 // sum of the DOT_BLOCKS partials of one vector by one wave, fixed order
 __device__ __forceinline__ double2 reduce_partials(const double2* __restrict__ p, int lane) {
     double sr = 0.0, si = 0.0;
@@ -59,10 +69,12 @@ __device__ __forceinline__ double2 reduce_partials(const double2* __restrict__ p
 // not bandwidth, bounds this kernel at |theta| ~ 10^5); the reductions are the in-wave butterfly plus one fixed-order sum over
 // the four waves of a slice.  CH = vectors per pass (compile time, so the loads are unconditional and can all be in flight;
 // indices past nvec are clamped and their sums discarded).
-template <int CH, int TH>
+// FZ: the rows are Q[0..nf) and then V[upd0 ..] (the two row ranges of the projected first pass), nvec rows in all.
+template <int CH, int TH, bool FZ>
 __global__ __launch_bounds__(TH) void k_dots_partial(const double2* __restrict__ V, int64_t ldv, int nvec,
                                                       const double2* __restrict__ w, int64_t n,
-                                                      double2* __restrict__ partial) {
+                                                      double2* __restrict__ partial, const double2* __restrict__ Q, int nf,
+                                                      int upd0) {
     // TH / 64 waves per slice: a wave keeps CH + 1 loads in flight per lane and the kernel is bound by the latency of that
     // one batch -- 256 waves on 256 CUs moved 4.7 TB/s; the waves' shares are summed in fixed wave order
     __shared__ double red[TH / 64][CH][2];
@@ -80,7 +92,7 @@ __global__ __launch_bounds__(TH) void k_dots_partial(const double2* __restrict__
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 const int i = i0 + c < nvec ? i0 + c : nvec - 1;
-                a[c] = V[(int64_t)i * ldv + j];
+                a[c] = lan_row<FZ>(V, Q, ldv, nf, FZ && i >= nf ? i + upd0 : i)[j];
             }
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
@@ -114,7 +126,18 @@ __global__ __launch_bounds__(TH) void k_dots_partial(const double2* __restrict__
 
 static void launch_dots_partial(const double2* V, int64_t ldv, int nvec, const double2* w, int64_t n, double2* partial,
                                 hipStream_t st) {
-#define HTN_DP(CHV, THV) hipLaunchKernelGGL((k_dots_partial<CHV, THV>), dim3(DOT_BLOCKS), dim3(THV), 0, st, V, ldv, nvec, w, n, partial)
+#define HTN_DP(CHV, THV)                                                                                                     \
+    hipLaunchKernelGGL((k_dots_partial<CHV, THV, false>), dim3(DOT_BLOCKS), dim3(THV), 0, st, V, ldv, nvec, w, n, partial, \
+                       (const double2*)nullptr, 0, 0)
+    HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_DP);
+#undef HTN_DP
+}
+// rows Q[0..nf) and V[upd0 .. upd0 + nvec - nf)
+static void launch_dots_partial_fz(const double2* V, int64_t ldv, int nvec, const double2* w, int64_t n, double2* partial,
+                                   const double2* Q, int nf, int upd0, hipStream_t st) {
+#define HTN_DP(CHV, THV)                                                                                                    \
+    hipLaunchKernelGGL((k_dots_partial<CHV, THV, true>), dim3(DOT_BLOCKS), dim3(THV), 0, st, V, ldv, nvec, w, n, partial, Q, \
+                       nf, upd0)
     HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_DP);
 #undef HTN_DP
 }
@@ -130,12 +153,13 @@ __global__ void k_dots_reduce(const double2* __restrict__ partial, int nvec, dou
 // to *c_out (a device scalar: the next matvec launch hands it to the host inside the step record).  CH = vectors per pass
 // (compile time): all basis loads of an element are in flight together (the earlier version walked them eight at a time, one
 // memory round trip per group of eight).
-template <int CH, int TH>
+template <int CH, int TH, bool FZ>
 __global__ __launch_bounds__(TH) void k_axpy_norm(double2* __restrict__ w, const double2* __restrict__ V,
                                                            int64_t ldv, int nvec,
                                                            const double2* __restrict__ partial,
                                                            double2* __restrict__ c_out, int c_index, double sign,
-                                                           int64_t n, double* __restrict__ norm_partial) {
+                                                           int64_t n, double* __restrict__ norm_partial,
+                                                           const double2* __restrict__ Q, int nf) {
     __shared__ double cs[64][2];
     __shared__ double red[TH / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -158,7 +182,7 @@ __global__ __launch_bounds__(TH) void k_axpy_norm(double2* __restrict__ w, const
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const int i = c < nvec ? c : nvec - 1;
-            v[c] = V[(int64_t)i * ldv + j];
+            v[c] = lan_row<FZ>(V, Q, ldv, nf, i)[j];
         }
         double2 x = w[j];
         double sr = 0.0, si = 0.0;
@@ -186,8 +210,17 @@ __global__ __launch_bounds__(TH) void k_axpy_norm(double2* __restrict__ w, const
 static void launch_axpy_norm(double2* w, const double2* V, int64_t ldv, int nvec, const double2* partial, double2* c_out, int c_index,
                              double sign, int64_t n, double* norm_partial, hipStream_t st) {
 #define HTN_AN(CHV, THV)                                                                                                    \
-    hipLaunchKernelGGL((k_axpy_norm<CHV, THV>), dim3(DOT_BLOCKS), dim3(THV), 0, st, w, V, ldv, nvec, partial, c_out, c_index, \
-                       sign, n, norm_partial)
+    hipLaunchKernelGGL((k_axpy_norm<CHV, THV, false>), dim3(DOT_BLOCKS), dim3(THV), 0, st, w, V, ldv, nvec, partial, c_out, \
+                       c_index, sign, n, norm_partial, (const double2*)nullptr, 0)
+    HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_AN);
+#undef HTN_AN
+}
+static void launch_axpy_norm_fz(double2* w, const double2* V, int64_t ldv, int nvec, const double2* partial, double2* c_out,
+                                int c_index, double sign, int64_t n, double* norm_partial, const double2* Q, int nf,
+                                hipStream_t st) {
+#define HTN_AN(CHV, THV)                                                                                                   \
+    hipLaunchKernelGGL((k_axpy_norm<CHV, THV, true>), dim3(DOT_BLOCKS), dim3(THV), 0, st, w, V, ldv, nvec, partial, c_out, \
+                       c_index, sign, n, norm_partial, Q, nf)
     HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_AN);
 #undef HTN_AN
 }
@@ -201,13 +234,16 @@ static void launch_axpy_norm(double2* w, const double2* V, int64_t ldv, int nvec
 // that row anyway, so it does the previous step's normalisation on the way: s = 1 / beta, the row is written back as
 // v = s raw, w is taken as s w, and the dots of K2 (taken with the raw row and the raw w) become c_i = s P_i (i < nvec-1),
 // c_last = s^2 P_last.  The separate scale kernel of every step is gone; its record is published by the next matvec launch.
-template <int CH, int TH>
+// FZ: rows 0..nf-1 are the frozen rows (normalised, never written), upd0 >= nf, and partial_in holds the dots of the rows
+// [0, nf) followed by those of [upd0, nvec): both ranges are subtracted, the Krylov rows between them are not.
+template <int CH, int TH, bool FZ>
 __global__ __launch_bounds__(TH) void k_axpy_dots(double2* __restrict__ w, double2* __restrict__ V,
                                                            int64_t ldv, int nvec,
                                                            const double2* __restrict__ partial_in,
                                                            double2* __restrict__ c_out, int c_index, double sign,
                                                            int64_t n, double2* __restrict__ partial_out,
-                                                           const double* __restrict__ norm_prev, int upd0) {
+                                                           const double* __restrict__ norm_prev, int upd0,
+                                                           const double2* __restrict__ Q, int nf) {
     __shared__ double cs[64][2];
     __shared__ double red[TH / 64][CH][2];
     __shared__ double s_scale;
@@ -228,8 +264,10 @@ __global__ __launch_bounds__(TH) void k_axpy_dots(double2* __restrict__ w, doubl
     const double s = s_scale;
     // partial_in holds the dots of rows upd0 .. nvec-1 only (the three-term first pass: upd0 = nvec - 2); the rows below
     // take no part in this update (coefficient 0) but do in the dots taken on the way
-    for (int i = upd0 + wave; i < nvec; i += TH / 64) {
-        double2 r = reduce_partials(partial_in + (int64_t)(i - upd0) * DOT_BLOCKS, lane);
+    const int skip = FZ ? upd0 - nf : upd0;           // rows [FZ ? nf : 0, upd0) have no entry in partial_in
+    for (int p = (FZ ? 0 : upd0) + wave; p < (FZ ? nvec - skip : nvec); p += TH / 64) {
+        const int i = FZ && p >= nf ? p + skip : p;
+        double2 r = reduce_partials(partial_in + (int64_t)(FZ ? p : i - upd0) * DOT_BLOCKS, lane);
         const bool raw_row = norm_prev && i == last;   // the row this coefficient multiplies is still unnormalised
         const double f = raw_row ? s * s : s;
         r.x *= f;
@@ -241,9 +279,10 @@ __global__ __launch_bounds__(TH) void k_axpy_dots(double2* __restrict__ w, doubl
             if (blockIdx.x == 0 && i == c_index) *c_out = r;
         }
     }
-    if ((tid >= nvec || tid < upd0) && tid < 64) cs[tid][0] = cs[tid][1] = 0.0;
+    if ((tid >= nvec || (tid < upd0 && !(FZ && tid < nf))) && tid < 64) cs[tid][0] = cs[tid][1] = 0.0;
     __syncthreads();
     const bool fix = norm_prev != nullptr;
+    double2* const vlast = V + (int64_t)(FZ ? last - nf : last) * ldv;
     const int64_t per = (n + DOT_BLOCKS - 1) / DOT_BLOCKS;
     const int64_t lo = (int64_t)blockIdx.x * per;
     const int64_t hi = lo + per < n ? lo + per : n;
@@ -255,11 +294,11 @@ __global__ __launch_bounds__(TH) void k_axpy_dots(double2* __restrict__ w, doubl
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const int i = c < nvec ? c : nvec - 1;
-            v[c] = V[(int64_t)i * ldv + j];
+            v[c] = lan_row<FZ>(V, Q, ldv, nf, i)[j];
         }
         if (fix) {                                    // (uniform) the newest row goes back normalised; v[] keeps it RAW: its factor s
-            const double2 vl = V[(int64_t)last * ldv + j];      // sits in its coefficient (above) and in its dot (below) -- no per-row select
-            V[(int64_t)last * ldv + j] = make_double2(vl.x * s, vl.y * s);
+            const double2 vl = vlast[j];              // sits in its coefficient (above) and in its dot (below) -- no per-row select
+            vlast[j] = make_double2(vl.x * s, vl.y * s);
         }
         double sr = 0.0, si = 0.0;
 #pragma unroll
@@ -305,9 +344,18 @@ __global__ __launch_bounds__(TH) void k_axpy_dots(double2* __restrict__ w, doubl
 static void launch_axpy_dots(double2* w, double2* V, int64_t ldv, int nvec, const double2* partial_in, double2* c_out,
                              int c_index, double sign, int64_t n, double2* partial_out, const double* norm_prev, int upd0,
                              hipStream_t st) {
-#define HTN_AD(CHV, THV)                                                                                           \
-    hipLaunchKernelGGL((k_axpy_dots<CHV, THV>), dim3(DOT_BLOCKS), dim3(THV), 0, st, w, V, ldv, nvec, partial_in, c_out, \
-                       c_index, sign, n, partial_out, norm_prev, upd0)
+#define HTN_AD(CHV, THV)                                                                                                  \
+    hipLaunchKernelGGL((k_axpy_dots<CHV, THV, false>), dim3(DOT_BLOCKS), dim3(THV), 0, st, w, V, ldv, nvec, partial_in, c_out, \
+                       c_index, sign, n, partial_out, norm_prev, upd0, (const double2*)nullptr, 0)
+    HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_AD);
+#undef HTN_AD
+}
+static void launch_axpy_dots_fz(double2* w, double2* V, int64_t ldv, int nvec, const double2* partial_in, double2* c_out,
+                                int c_index, double sign, int64_t n, double2* partial_out, const double* norm_prev, int upd0,
+                                const double2* Q, int nf, hipStream_t st) {
+#define HTN_AD(CHV, THV)                                                                                                 \
+    hipLaunchKernelGGL((k_axpy_dots<CHV, THV, true>), dim3(DOT_BLOCKS), dim3(THV), 0, st, w, V, ldv, nvec, partial_in, c_out, \
+                       c_index, sign, n, partial_out, norm_prev, upd0, Q, nf)
     HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_AD);
 #undef HTN_AD
 }
@@ -577,22 +625,26 @@ void htn_krylov_release_stream(hipStream_t st) {
     g_lan_res.erase(st);
 }
 
-extern "C" int htn_lanczos_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot,
-                             void* Vv, int64_t n, int32_t krylovdim, double tol, int32_t max_restart,
-                             void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
-                             double* eig_host, int32_t* n_matvec_host, double* residual_host,
-                             double* matvec_ms_host, void* stream_v) {
+// The driver of htn_lanczos_z (nf = 0) and htn_lanczos_orth_z (nf frozen rows Q: lowest eigenpair of P H P, P = 1 - Q Q^H).
+// With frozen rows every pass of a step runs over Q followed by the Krylov rows: the first (short) pass takes the dots with
+// Q AND {V[j-1], V[j]} -- H v_j has O(|H|) components along Q, not O(eps |H|) -- and the second pass is the full one it always
+// was; alpha_j, the deferred normalisation, the records and the pipeline do not change.  nf = 0 enqueues exactly the kernels,
+// arguments and order of the driver before frozen rows existed.
+static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot,
+                       void* Vv, int64_t n, int32_t krylovdim, double tol, int32_t max_restart,
+                       void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
+                       double* eig_host, int32_t* n_matvec_host, double* residual_host,
+                       double* matvec_ms_host, void* stream_v, const double2* Q, int nf) {
     hipStream_t st = (hipStream_t)stream_v;
     const int kd = krylovdim;
-    // (k_axpy_dots keeps one basis value per Krylov vector in registers: at most DOT_CHUNK = 32 vectors per step)
-    if (kd < 2 || kd + 1 > DOT_CHUNK) return fail_msg("htn_lanczos_z: krylovdim must be in 2..31");
+    const int kt = kd + nf;                                        // rows of the widest pass + 1
     double2* V = (double2*)Vv;
     double2* partial = (double2*)scratch;
-    double2* partial2 = partial + (int64_t)(kd + 1) * DOT_BLOCKS;
-    double2* c1 = partial2 + (int64_t)(kd + 1) * DOT_BLOCKS;      // device scalars <v_j, w>: first / second pass
-    double2* c2 = c1 + (kd + 1);
-    double2* ycoef = c2 + (kd + 1);
-    double* norm_partial = (double*)(ycoef + (kd + 1));
+    double2* partial2 = partial + (int64_t)(kt + 1) * DOT_BLOCKS;
+    double2* c1 = partial2 + (int64_t)(kt + 1) * DOT_BLOCKS;      // device scalars <v_j, w>: first / second pass
+    double2* c2 = c1 + (kt + 1);
+    double2* ycoef = c2 + (kt + 1);
+    double* norm_partial = (double*)(ycoef + (kt + 1));
 
     LanRes* R = nullptr;
     if (lan_res_get(st, &R)) return 1;
@@ -646,9 +698,16 @@ extern "C" int htn_lanczos_z(const htn_gemm_launch* stages, int32_t n_stages, in
         // which is what the second pass of a two-pass scheme delivers.  (Until round 3 the first pass was a full one as well:
         // one more read of the whole basis per step; HTN_LANCZOS_FULL_FIRST_PASS=1 brings it back for comparison.)
         const int upd0 = full_first_pass || j < 2 ? 0 : j - 1;
-        launch_dots_partial(V + (int64_t)upd0 * n, n, j + 1 - upd0, w, n, partial, st);
-        launch_axpy_dots(w, V, n, j + 1, partial, c1 + j, j, -1.0, n, partial2, first ? (const double*)nullptr : norm_partial, upd0, st);
-        launch_axpy_norm(w, V, n, j + 1, partial2, c2 + j, j, -1.0, n, norm_partial, st);
+        if (nf == 0) {
+            launch_dots_partial(V + (int64_t)upd0 * n, n, j + 1 - upd0, w, n, partial, st);
+            launch_axpy_dots(w, V, n, j + 1, partial, c1 + j, j, -1.0, n, partial2, first ? (const double*)nullptr : norm_partial, upd0, st);
+            launch_axpy_norm(w, V, n, j + 1, partial2, c2 + j, j, -1.0, n, norm_partial, st);
+        } else {
+            launch_dots_partial_fz(V, n, nf + j + 1 - upd0, w, n, partial, Q, nf, upd0, st);
+            launch_axpy_dots_fz(w, V, n, nf + j + 1, partial, c1 + j, nf + j, -1.0, n, partial2,
+                                first ? (const double*)nullptr : norm_partial, nf + upd0, Q, nf, st);
+            launch_axpy_norm_fz(w, V, n, nf + j + 1, partial2, c2 + j, nf + j, -1.0, n, norm_partial, Q, nf, st);
+        }
         if (j == kd - 1) {
             hipLaunchKernelGGL(k_publish_record, dim3(1), dim3(64), 0, st, (const double*)norm_partial, (const double2*)(c1 + j),
                                (const double2*)(c2 + j), R->d_rec + j, step_serial[j]);
@@ -688,7 +747,16 @@ extern "C" int htn_lanczos_z(const htn_gemm_launch* stages, int32_t n_stages, in
         }
     };
 
-    // normalise the start vector
+    // w -= Q (Q^H w), twice; the second update leaves |w|^2 in norm_partial (c_index -1: no coefficient is published)
+    auto project_out = [&](double2* w) {
+        for (int pass = 0; pass < 2; ++pass) {
+            launch_dots_partial(Q, n, nf, w, n, partial, st);
+            launch_axpy_norm(w, Q, n, nf, partial, c1, -1, -1.0, n, norm_partial, st);
+        }
+    };
+    // normalise the start vector (frozen rows: projected first)
+    if (nf > 0) project_out(V);
+    else
     hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, n, norm_partial);
     hipLaunchKernelGGL(k_scale_by_norm, dim3(grid_for(n)), dim3(DOT_THREADS), 0, st, V, V, norm_partial, n,
                        (LanRecord*)nullptr, (const double2*)nullptr, (const double2*)nullptr, 0ull);
@@ -748,6 +816,10 @@ extern "C" int htn_lanczos_z(const htn_gemm_launch* stages, int32_t n_stages, in
         double2* xrow = V + (int64_t)(kd + 1) * n;
         HIP_TRY(hipMemsetAsync(xrow, 0, sizeof(double2) * n, st));
         hipLaunchKernelGGL(k_axpys, dim3(grid_for(n)), dim3(256), 0, st, xrow, V, n, k, ycoef, 1.0, n);
+        // (frozen rows: the Ritz vector is a combination of Krylov rows that are orthogonal to Q to rounding each; projecting
+        // the sum once more keeps |Q^H x| at rounding whatever the number of rows)
+        if (nf > 0) project_out(xrow);
+        else
         hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, xrow, n, norm_partial);
         hipLaunchKernelGGL(k_scale_by_norm, dim3(grid_for(n)), dim3(DOT_THREADS), 0, st, V, xrow, norm_partial, n,
                            (LanRecord*)nullptr, (const double2*)nullptr, (const double2*)nullptr, 0ull);
@@ -764,4 +836,28 @@ extern "C" int htn_lanczos_z(const htn_gemm_launch* stages, int32_t n_stages, in
     // sampled launches scaled to all launches of this solve (the next solves continue the 1-in-8 sampling phase)
     if (matvec_ms_host) *matvec_ms_host = n_timed ? mv_ms * nmv / n_timed : -1.0;
     return 0;
+}
+
+extern "C" int htn_lanczos_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot,
+                             void* Vv, int64_t n, int32_t krylovdim, double tol, int32_t max_restart,
+                             void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
+                             double* eig_host, int32_t* n_matvec_host, double* residual_host,
+                             double* matvec_ms_host, void* stream_v) {
+    // (k_axpy_dots keeps one basis value per Krylov vector in registers: at most DOT_CHUNK = 32 vectors per step)
+    if (krylovdim < 2 || krylovdim + 1 > DOT_CHUNK) return fail_msg("htn_lanczos_z: krylovdim must be in 2..31");
+    return lanczos_run(stages, n_stages, x_slot, y_slot, Vv, n, krylovdim, tol, max_restart, scratch, zero_y, exchange, user,
+                       eig_host, n_matvec_host, residual_host, matvec_ms_host, stream_v, nullptr, 0);
+}
+
+extern "C" int htn_lanczos_orth_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot,
+                                  void* Vv, int64_t n, int32_t krylovdim, double tol, int32_t max_restart,
+                                  void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
+                                  double* eig_host, int32_t* n_matvec_host, double* residual_host,
+                                  double* matvec_ms_host, const void* Q, int32_t n_frozen, void* stream_v) {
+    // (the frozen rows sit in the same registers as the Krylov rows: one basis value per row, DOT_CHUNK = 32 rows per pass)
+    if (n_frozen < 0 || (n_frozen > 0 && !Q)) return fail_msg("htn_lanczos_orth_z: n_frozen rows need a device pointer Q");
+    if (krylovdim < 2 || krylovdim + n_frozen + 1 > DOT_CHUNK)
+        return fail_msg("htn_lanczos_orth_z: krylovdim >= 2 and krylovdim + n_frozen <= 31 required");
+    return lanczos_run(stages, n_stages, x_slot, y_slot, Vv, n, krylovdim, tol, max_restart, scratch, zero_y, exchange, user,
+                       eig_host, n_matvec_host, residual_host, matvec_ms_host, stream_v, (const double2*)Q, n_frozen);
 }

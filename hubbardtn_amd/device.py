@@ -217,7 +217,12 @@ class HipOps:
         abi.check(self.lib, self.lib.htn_scale_inv_sqrt_z(self._p(dst), self._p(src), self._p(nrm2), n,
                                                           self._stream()), "htn_scale_inv_sqrt_z")
 
-    def lanczos(self, stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, zero_y=False, exchange=None):
+    def lanczos_orth(self, stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, Q, n_frozen):
+        """htn_lanczos_orth_z: lanczos() inside the orthogonal complement of the n_frozen orthonormal rows Q (device tensor,
+        row r at Q[r * n : (r + 1) * n]; None with n_frozen = 0).  Returns (eigenvalue, n_matvec, residual)."""
+        return self.lanczos(stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, frozen=(Q, int(n_frozen)))
+
+    def lanczos(self, stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, zero_y=False, exchange=None, frozen=None):
         """lowest eigenpair of the map defined by `stages` = [(bufs, dev_tasks), ...]; V[0:n] start -> result.
         exchange(y_tensor) is called after every matvec has been enqueued (multi-GPU all-reduce hook).
         Returns (eigenvalue, n_matvec, residual)."""
@@ -228,7 +233,7 @@ class HipOps:
                 arr[k].bufs[b] = 0 if bufs[b] is None else bufs[b].data_ptr()
             arr[k].tiles, arr[k].segs, arr[k].n_tiles = tiles.data_ptr(), segs.data_ptr(), ntiles
             keep.append((bufs, tiles, segs))
-        need = self.lib.htn_lanczos_scratch_elems(krylovdim)
+        need = self.lib.htn_lanczos_scratch_elems(krylovdim + (frozen[1] if frozen else 0))
         if getattr(self, "_lan_scratch", None) is None or self._lan_scratch.numel() < need:
             self._lan_scratch = self.empty_z(need)
         base = V.data_ptr()
@@ -246,13 +251,20 @@ class HipOps:
         cb = abi.EXCHANGE_FN(_cb) if exchange is not None else abi.EXCHANGE_FN()
         eig, nmv, res, ms = C.c_double(0.0), C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
         timed = self.event_log is not None
-        rc = self.lib.htn_lanczos_z(arr, len(stages), x_slot, y_slot, self._p(V), n, krylovdim,
-                                    float(tol), max_restart, self._p(self._lan_scratch),
-                                    1 if zero_y else 0, cb, None, C.byref(eig), C.byref(nmv),
-                                    C.byref(res), C.byref(ms) if timed else None, self._stream())
+        if frozen is None:
+            rc = self.lib.htn_lanczos_z(arr, len(stages), x_slot, y_slot, self._p(V), n, krylovdim,
+                                        float(tol), max_restart, self._p(self._lan_scratch),
+                                        1 if zero_y else 0, cb, None, C.byref(eig), C.byref(nmv),
+                                        C.byref(res), C.byref(ms) if timed else None, self._stream())
+        else:
+            rc = self.lib.htn_lanczos_orth_z(arr, len(stages), x_slot, y_slot, self._p(V), n, krylovdim,
+                                             float(tol), max_restart, self._p(self._lan_scratch),
+                                             1 if zero_y else 0, cb, None, C.byref(eig), C.byref(nmv),
+                                             C.byref(res), C.byref(ms) if timed else None,
+                                             None if frozen[0] is None else self._p(frozen[0]), frozen[1], self._stream())
         if err:
             raise err[0]
-        abi.check(self.lib, rc, "htn_lanczos_z")
+        abi.check(self.lib, rc, "htn_lanczos_z" if frozen is None else "htn_lanczos_orth_z")
         if timed:
             self.event_log.append(("matvec_ms", ms.value, nmv.value))
         return eig.value, nmv.value, res.value

@@ -221,6 +221,28 @@ class DMRG2:
             chk()
         abi.check(self.lib, rc, what)
 
+    # ---- excited states: orthogonalised sweeps (htn_mps_set_orthogonal) --------------------------------
+    def set_orthogonal(self, others=()):
+        """keep every optimising update in the orthogonal complement of the given engines' states (same context, symmetry,
+        chain length and total sector; at most 8; krylovdim + len(others) <= 31).  They must not be swept while attached;
+        an empty list detaches.  The library holds its own references to the attached states."""
+        others = list(others)
+        arr = (C.c_void_p * max(len(others), 1))(*[o.handle for o in others])
+        self._check(self.lib.htn_mps_set_orthogonal(self.handle, arr, len(others)), "htn_mps_set_orthogonal")
+        self.attached = others
+
+    def overlap(self, other) -> complex:
+        """<self|other> by a transfer pass on the device"""
+        out = (C.c_double * 2)()
+        self._check(self.lib.htn_mps_overlap(self.handle, other.handle, out), "htn_mps_overlap")
+        return complex(out[0], out[1])
+
+    def dropped_projectors(self) -> int:
+        """projector rows the last bond update dropped as numerically dependent on the others"""
+        d = C.c_int32(0)
+        self.lib.htn_mps_orthogonal_count(self.handle, C.byref(d))
+        return d.value
+
     # ---- options ----------------------------------------------------------------------------------
     def _opts(self, cutoff=None):
         return sweep_opts(self.chi_full, self.cutoff if cutoff is None else cutoff, self.krylovdim, self.lanczos_tol,

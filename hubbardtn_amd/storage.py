@@ -73,6 +73,31 @@ def cache_name(simul, what="groundstate"):
     return sub, f"{prefix}_{tail}"
 
 
+def excitations_name(simul, nums, charges, trunc_dim=0):
+    """(sub-directory, file stem) of a produce_excitations entry: the reference's prefix rule (src:1230-1263) --
+    exc_[spin_]<t..u..J..U..m.._.._><code>_N=<nums>c=f<parity>su<spin>u<dN>_tr=<trunc_dim>, "__" -> "_" -- followed by
+    savename(simul) and the chain length.  The reference's momentum part `_k=..` has no finite-chain counterpart (an open
+    chain has no momentum) and is left out."""
+    spin = bool(simul.kwargs.get("spin", False))
+    jl = lambda v: "[" + ", ".join(repr(float(x)) for x in v) + "]"
+    param = ""
+    if not isinstance(simul, MB_Sim):
+        U13 = simul.kwargs.get("U13", [0.0])
+        JMs = simul.kwargs.get("JMs", (0.0, 0.0))
+        param = f"t{jl(simul.t)}u{jl(simul.u)}J{jl(simul.J)}U{jl(U13)}m{float(JMs[0])!r}_{float(JMs[1])!r}_"
+    if isinstance(simul, (OBC_Sim2, MBC_Sim)):
+        charge = f"f{int(charges[0])}su{float(charges[1])!r}"
+    elif spin:
+        charge = f"f{int(charges[0])}u{float(charges[1])!r}u{int(charges[2])}"
+    else:
+        charge = f"f{int(charges[0])}su{float(charges[1])!r}u{int(charges[2])}"
+    prefix = "exc_" + ("spin_" if spin else "") + param + str(simul.kwargs.get("code", "")) + f"_N={int(nums)}c={charge}_tr={int(trunc_dim)}"
+    prefix = prefix.replace("__", "_").replace("3.141592653589793", "pi")
+    sub = {MBC_Sim: "MBC", OBC_Sim2: "OBC"}.get(type(simul), "MB" if isinstance(simul, MB_Sim) else "OB")
+    L = simul.kwargs.get("L")
+    return sub, f"{prefix}_{savename(simul)}" + (f"_L={int(L)}" if L else "")
+
+
 # ---- state <-> dictionaries ----------------------------------------------------------------------------------------
 def state_dicts(eng):
     """per-site dictionaries of an engine's MPS: [{'kind': 'L'|'R', 'blocks': {(l, s, r): matrix}}], and the bond tables"""

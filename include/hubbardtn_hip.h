@@ -133,6 +133,21 @@ int htn_lanczos_z(const htn_gemm_launch* stages_host, int32_t n_stages, int32_t 
                   double* eig_host, int32_t* n_matvec_host, double* residual_host,
                   double* matvec_ms_host /* NULL, or receives the HIP-event time of all matvec launches */,
                   void* stream);
+/* Lanczos with frozen rows: the lowest eigenpair of P H_eff P, P = 1 - Q Q^H, for n_frozen ORTHONORMAL device rows Q of
+ * length n (row r at Q + r * n).  The start vector is projected first; every Krylov vector is orthogonalised against Q in
+ * both passes of its step (the rows of a pass are Q followed by the Krylov rows); the Ritz vector is assembled from the
+ * Krylov rows only and projected once more, so |Q^H x| stays at rounding.  This is a projection, not an energy penalty:
+ * nothing to tune and the spectrum keeps its scale.  (Orthogonalised two-site DMRG for excited states; MPSKit reaches
+ * excitations through the quasiparticle ansatz instead, src/HubbardFunctions.jl:1173-1299.)
+ * The vector kernels keep one basis value per row in registers, 32 rows at most:
+ *     krylovdim >= 2  and  krylovdim + n_frozen <= 31,      anything else is an error.
+ * scratch: htn_lanczos_scratch_elems(krylovdim + n_frozen) elements; V and everything else as for htn_lanczos_z.
+ * n_frozen = 0 (Q may be NULL) enqueues exactly what htn_lanczos_z enqueues: same bits, same matvec count. */
+int htn_lanczos_orth_z(const htn_gemm_launch* stages_host, int32_t n_stages, int32_t x_slot, int32_t y_slot,
+                       void* V, int64_t n, int32_t krylovdim, double tol, int32_t max_restart, void* scratch,
+                       int32_t zero_y, htn_exchange2_fn exchange, void* user,
+                       double* eig_host, int32_t* n_matvec_host, double* residual_host, double* matvec_ms_host,
+                       const void* Q, int32_t n_frozen, void* stream);
 
 /* Batched one-sided Jacobi SVD of the coupled-sector blocks of a two-site tensor.
  * Stands in for: TensorKit tsvd!(t; alg=SVD()) -> LAPACK zgesvd per block (SURVEY.md 8a a9,
@@ -360,6 +375,23 @@ int htn_bond_update(htn_mps* mps, int32_t i, int32_t direction, int32_t placemen
 /* one sweep in MPSKit's DMRG2 order: bonds 1..L-1 rightwards, L-2..1 leftwards (2L-3 updates);
  * stats_host: 2L-3 records or NULL; energy_host receives the last eigenvalue */
 int htn_dmrg2_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* stats_host, double* energy_host);
+
+/* Excited states inside one sector: orthogonalised two-site DMRG.  After htn_mps_set_orthogonal(mps, others, n) every
+ * OPTIMISING bond update of `mps` finds the lowest eigenpair of H_eff inside the orthogonal complement of the n attached
+ * states: per attached state phi_k the overlap environments <mps|phi_k> of every bond are built at the call and moved with
+ * the H environment by every update (non-optimising moves included); per update p_k = O_L theta_phi O_R is formed in the
+ * state's theta layout (<p_k, theta> = <phi_k|psi>), the p_k are orthonormalised (a row whose remainder is below 1e-12 of
+ * its norm is dropped) and the solve is htn_lanczos_orth_z's.  krylovdim + n <= 31, else the update fails.
+ * The attached states must live in the same context and have the same symmetry, chain length and total sector (end
+ * bonds of one sector, dimension 1); any centre position; they must not be updated while attached (attach again after
+ * changing one).  References are counted: an attached state stays alive until it is detached.  n = 0 detaches; a state
+ * without attached states takes exactly the code path it took before this call existed.  At most 8 states.  Not available
+ * on a context with a communicator (htn_ctx_set_comm / htn_ctx_set_exchange with world > 1). */
+int htn_mps_set_orthogonal(htn_mps* mps, const htn_mps* const* others_host, int32_t n);
+/* -> number of attached states; dropped_host (may be NULL): projector rows dropped as dependent in the last update */
+int32_t htn_mps_orthogonal_count(const htn_mps* mps, int32_t* dropped_host);
+/* out_host[0..1] = <a|b> (re, im) by a transfer pass on the device; 0 for states in different total sectors */
+int htn_mps_overlap(htn_mps* a, const htn_mps* b, double* out_host);
 
 /* y = H_eff(bond i, i+1) x on host vectors in the library's theta layout (size htn_mps_theta_size); tests and
  * Hermiticity checks.  x and y are complex128 host arrays. */

@@ -402,6 +402,21 @@ function MPSKit.find_groundstate(ψ::InfiniteMPS, H, alg::HIPIDMRG2, envs = noth
         ccall((:htn_ctx_destroy, lib), Cvoid, (Ptr{Cvoid},), ctx[])
     end
 end
+# ---- excited states on finite chains: the two sweep-level calls (untested like the rest of this file) ---------------------
+# `mps`, `others`: htn_mps handles (Ptr{Cvoid}) of states in the same context, symmetry, chain length and total sector.
+# After set_orthogonal! every optimising htn_bond_update / htn_dmrg2_sweep of `mps` stays in the orthogonal complement of
+# `others` (krylovdim + length(others) <= 31, at most 8); an empty list detaches.  The library keeps its own references.
+function set_orthogonal!(mps::Ptr{Cvoid}, others::Vector{Ptr{Cvoid}})
+    check(ccall((:htn_mps_set_orthogonal, lib), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Int32), mps, others, Int32(length(others))))
+    return mps
+end
+# <a|b> by a transfer pass on the device
+function overlap(a::Ptr{Cvoid}, b::Ptr{Cvoid})
+    out = zeros(Float64, 2)
+    check(ccall((:htn_mps_overlap, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), a, b, out))
+    return complex(out[1], out[2])
+end
+
 # compute_groundstate's infinite-chain call (src:1010) then reads
 #     ψw, e, δ = find_groundstate(ψ₀, H, HubbardHIP.HIPIDMRG2(; trscheme = truncbelow(10.0^(-svalue)), tol = tol, P = P, Q = Q))
 # with e the energy per site the reference's expectation_value(ψ, H) / length(H) reports.
