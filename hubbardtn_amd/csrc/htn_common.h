@@ -6,6 +6,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <map>
+#include <memory>
+#include <mutex>
+#include <utility>
+
 #include "hubbardtn_hip.h"
 
 char* htn_err_buf();          // thread-local, 512 bytes (htn_abi.hip)
@@ -96,9 +101,84 @@ struct HtnGemmPublish {
 int htn_grouped_gemm_launch(const void* const* bufs_host, const htn_tile* tiles, int32_t n_tiles, const htn_seg* segs,
                             const HtnGemmPublish* pub, hipStream_t stream);
 
-// per-stream scratch of the multi-launch drivers (htn_krylov.hip, htn_svd.hip): owned by the stream's registry entry,
-// released by the backend that owns the stream (HipBackend::~HipBackend) -- nothing thread-local, nothing shared between
-// two contexts.  A caller of the kernel-level ABI that brings its own stream keeps its entry until the process ends.
+// ---- host-side scratch and per-stream resources of the multi-launch drivers (htn_krylov.hip, htn_svd.hip) ---------------
+// One allocation of one kind that only grows: reserve(bytes) reallocates with a slack factor of 2 when the request exceeds
+// the capacity (the old contents are NOT kept) and frees in the destructor -- the owner sets the device first.  New device
+// memory is filled with 0xFF bytes under HTN_DEBUG_POISON unless the owner declares it fully written before every use.
+enum HtnBufKind {
+    HTN_BUF_DEVICE,      // hipMalloc
+    HTN_BUF_PINNED,      // hipHostMalloc: host -> device staging
+    HTN_BUF_MAPPED       // hipHostMalloc mapped + coherent, device -> host; dev is the device view of it
+};
+struct HtnBuf {
+    const HtnBufKind kind;
+    const bool poison;
+    void* p = nullptr;        // device pointer (HTN_BUF_DEVICE), host pointer otherwise
+    void* dev = nullptr;      // HTN_BUF_MAPPED: the device view; HTN_BUF_DEVICE: p
+    size_t cap = 0;           // bytes
+    explicit HtnBuf(HtnBufKind k, bool poison_new = true) : kind(k), poison(poison_new) {}
+    HtnBuf(const HtnBuf&) = delete;      // (not assignable either: const members)
+    ~HtnBuf() { (void)release(); }
+    hipError_t release() {
+        const hipError_t e = !p ? hipSuccess : (kind == HTN_BUF_DEVICE ? hipFree(p) : hipHostFree(p));
+        p = dev = nullptr, cap = 0;
+        return e;
+    }
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return 0;
+        HIP_TRY(release());
+        const size_t want = bytes * 2;
+        if (kind == HTN_BUF_DEVICE) {
+            HIP_TRY(hipMalloc(&p, want));
+            dev = p;
+            if (poison && htn_debug_poison()) HIP_TRY(hipMemset(p, 0xFF, want));
+        } else if (kind == HTN_BUF_PINNED) {
+            HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+        } else {
+            HIP_TRY(hipHostMalloc(&p, want, hipHostMallocMapped | hipHostMallocCoherent));
+            HIP_TRY(hipHostGetDevicePointer(&dev, p, 0));
+        }
+        cap = want;
+        return 0;
+    }
+};
+
+// Registry of per-stream driver resources: T has an `int device` member and a destructor that sets that device before it
+// frees.  Keyed by (current device, stream): the default stream is handle 0 on EVERY device, so the stream alone does not
+// name an entry.  An entry is owned by the registry and released by the backend that owns the stream
+// (HipBackend::~HipBackend) -- nothing thread-local, nothing shared between two contexts.  A caller of the kernel-level ABI
+// that brings its own stream keeps its entry until the process ends.
+template <class T>
+class HtnStreamRegistry {
+    std::mutex mu;
+    std::map<std::pair<int, hipStream_t>, std::unique_ptr<T>> entries;
+
+public:
+    // the entry of `st` on the current device; a new one is set up by init(T&) -> int under the lock, and an init that fails
+    // leaves no entry behind
+    template <class Init>
+    int get(hipStream_t st, T** out, Init init) {
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = entries.find({dev, st});
+        if (it == entries.end()) {
+            auto r = std::make_unique<T>();
+            r->device = dev;
+            if (init(*r)) return 1;
+            it = entries.emplace(std::make_pair(dev, st), std::move(r)).first;
+        }
+        *out = it->second.get();
+        return 0;
+    }
+    void release(hipStream_t st) {      // the entry of `st` on the CURRENT device, if any
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return;
+        std::lock_guard<std::mutex> lk(mu);
+        entries.erase({dev, st});
+    }
+};
+// release the entry of `st` on the current device (HipBackend::~HipBackend sets its device before it calls these)
 void htn_krylov_release_stream(hipStream_t st);
 void htn_svd_release_stream(hipStream_t st);
 

@@ -12,10 +12,6 @@
 #include <math.h>
 
 #include <chrono>
-
-#include <map>
-#include <memory>
-#include <mutex>
 #include <vector>
 
 #include "htn_common.h"
@@ -594,36 +590,26 @@ struct LanRes {
             }
     }
 };
-std::mutex g_lan_mu;
-std::map<hipStream_t, std::unique_ptr<LanRes>> g_lan_res;
+HtnStreamRegistry<LanRes> g_lan_res;
 
 int lan_res_get(hipStream_t st, LanRes** out) {
-    std::lock_guard<std::mutex> lk(g_lan_mu);
-    auto& slot = g_lan_res[st];
-    if (!slot) {
-        auto r = std::make_unique<LanRes>();
-        HIP_TRY(hipGetDevice(&r->device));
-        HIP_TRY(hipHostMalloc((void**)&r->h_rec, sizeof(LanRecord) * LAN_SLOTS, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(r->h_rec, 0, sizeof(LanRecord) * LAN_SLOTS);      // (before any device work can see the block)
-        HIP_TRY(hipHostGetDevicePointer((void**)&r->d_rec, r->h_rec, 0));
-        HIP_TRY(hipHostMalloc((void**)&r->h_y, sizeof(double2) * LAN_SLOTS, hipHostMallocDefault));
+    return g_lan_res.get(st, out, [](LanRes& r) -> int {
+        HIP_TRY(hipHostMalloc((void**)&r.h_rec, sizeof(LanRecord) * LAN_SLOTS, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(r.h_rec, 0, sizeof(LanRecord) * LAN_SLOTS);      // (before any device work can see the block)
+        HIP_TRY(hipHostGetDevicePointer((void**)&r.d_rec, r.h_rec, 0));
+        HIP_TRY(hipHostMalloc((void**)&r.h_y, sizeof(double2) * LAN_SLOTS, hipHostMallocDefault));
         for (int i = 0; i < LAN_SLOTS; ++i) {
-            HIP_TRY(hipEventCreateWithFlags(&r->ev_done[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreate(&r->ev_mv0[i]));
-            HIP_TRY(hipEventCreate(&r->ev_mv1[i]));
+            HIP_TRY(hipEventCreateWithFlags(&r.ev_done[i], hipEventDisableTiming));
+            HIP_TRY(hipEventCreate(&r.ev_mv0[i]));
+            HIP_TRY(hipEventCreate(&r.ev_mv1[i]));
         }
-        r->have_events = true;
-        slot = std::move(r);
-    }
-    *out = slot.get();
-    return 0;
+        r.have_events = true;
+        return 0;
+    });
 }
 }  // namespace
 
-void htn_krylov_release_stream(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_lan_mu);
-    g_lan_res.erase(st);
-}
+void htn_krylov_release_stream(hipStream_t st) { g_lan_res.release(st); }
 
 // The driver of htn_lanczos_z (nf = 0) and htn_lanczos_orth_z (nf frozen rows Q: lowest eigenpair of P H P, P = 1 - Q Q^H).
 // With frozen rows every pass of a step runs over Q followed by the Krylov rows: the first (short) pass takes the dots with

@@ -1,4 +1,8 @@
 """GPU parity of every C-ABI primitive against its numpy statement (tests/emul.py)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -406,6 +410,10 @@ def test_batched_copy_matches_numpy(hip_ops):
 def test_lanczos_driver_matches_dense_eigh(hip_ops):
     """htn_lanczos_z on a Hermitian map given as one grouped-GEMM stage (y = H x, H dense 200x200 here,
     x stored as a 200 x 3 block so the stage exercises tiles + segments) vs numpy eigh"""
+    _lanczos_vs_dense_eigh(hip_ops)
+
+
+def _lanczos_vs_dense_eigh(hip_ops):
     rng = np.random.default_rng(6)
     m, nc = 200, 3
     H = _rand_z(rng, m * m).reshape(m, m)
@@ -498,3 +506,69 @@ def test_ring_jacobi_many_uneven_blocks_in_several_batches(hip_ops):
         Viso = out[:, live] / s[live]
         assert np.abs(Viso.conj().T @ Viso - np.eye(live.sum())).max() < 1e-12, i
         assert np.abs(np.linalg.norm(mats[i] @ Viso, axis=0) - s[live]).max() <= 1e-12 * ref[0], i
+
+
+def _ring_svd_vs_lapack(hip_ops):
+    """a batch with large (ring-path) blocks beside a small one, through the kernel-level jacobi_svd with the host copy
+    of the descriptors; checked like the batch test above"""
+    rng = np.random.default_rng(31)
+    shapes = [(202, 202), (60, 70), (230, 180)]
+    desc = np.zeros(len(shapes), dtype=abi.SVD_DT)
+    go = vo = so = 0
+    mats = []
+    for i, (m0, n0) in enumerate(shapes):
+        r = min(m0, n0)
+        desc[i] = (go, vo, so, n0, r, abi.SVD_QRCP, m0)
+        U, _ = np.linalg.qr(_rand_z(rng, m0 * r).reshape(m0, r))
+        W, _ = np.linalg.qr(_rand_z(rng, n0 * r).reshape(n0, r))
+        s = 10.0 ** (-9 * np.arange(r) / max(r - 1, 1)) * (1.0 + 0.3 * i)
+        mats.append((U * s) @ W.conj().T)
+        go, vo, so = go + m0 * n0, vo + ((n0 + 63) // 64 * 64) * r, so + r
+    dG = hip_ops.to_device(np.concatenate([M.T.reshape(-1) for M in mats]))
+    dV, dS, info = hip_ops.zeros_z(vo), hip_ops.empty_f64(so), hip_ops.empty_i32(len(shapes))
+    used = hip_ops.jacobi_svd(dG, dV, dS, hip_ops.to_device(desc), len(shapes), 230, 40, 1e-14, info, desc_host=desc)
+    Gp, S, inf = hip_ops.to_host(dG), hip_ops.to_host(dS), hip_ops.to_host(info)
+    assert inf.min() >= 0 and inf.max() <= 13 and 1 <= used <= 13, (inf, used)      # used >= 1: a block took the large path
+    for i, (m0, n0) in enumerate(shapes):
+        d = desc[i]
+        r = min(m0, n0)
+        out = Gp[d["g_off"]:d["g_off"] + n0 * r].reshape(r, n0).T
+        s = S[d["s_off"]:d["s_off"] + r]
+        ref = np.linalg.svd(mats[i], compute_uv=False)
+        order = np.argsort(-s)
+        assert np.abs(s[order] - ref).max() <= 1e-13 * ref[0], i
+        big = ref > 1e-6 * ref[0]
+        assert np.abs(s[order][big] / ref[big] - 1).max() < 1e-8, i
+        live = s > 1e-12 * ref[0]
+        Viso = out[:, live] / s[live]
+        assert np.abs(Viso.conj().T @ Viso - np.eye(live.sum())).max() < 1e-12, i
+        assert np.abs(np.linalg.norm(mats[i] @ Viso, axis=0) - s[live]).max() <= 1e-12 * ref[0], i
+
+
+def test_default_stream_of_two_devices_in_one_process():
+    """the drivers' per-stream resources are keyed by (device, stream): the default stream is handle 0 on every device, so
+    keyed by the stream alone a second device would be handed the scratch, forked stream and events of the first.  One
+    fresh child process (its own HipOps(0) and HipOps(1); the session's hip_ops and torch's current device stay as they
+    are) runs the large-block SVD and the Lanczos driver on the default stream of device 0, of device 1, and of device 0
+    again; every result is checked against numpy in the child."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    assert "RESULT two devices ok" in p.stdout, p.stdout[-2000:]
+
+
+if __name__ == "__main__":
+    from hubbardtn_amd.device import HipOps
+    alive = []                       # (a context that goes away makes ITS device the current one)
+    for dev in (0, 1, 0):
+        ops = HipOps(dev)            # makes `dev` the current device; the kernel-level calls run on its default stream
+        alive.append(ops)
+        _ring_svd_vs_lapack(ops)
+        _lanczos_vs_dense_eigh(ops)
+        ops.sync()
+    print("RESULT two devices ok")
