@@ -100,8 +100,13 @@ class NumpyOps:
     def scale_inv_sqrt(self, dst, src, nrm2, n):
         dst[:n] = src[:n] / np.sqrt(nrm2[0].real)
 
-    def lanczos(self, stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, zero_y=False, exchange=None):
-        """numpy statement of htn_lanczos_z (same algorithm: CGS2 full reorthogonalisation, eager stop)"""
+    def lanczos(self, stages, x_slot, y_slot, V, n, krylovdim, tol, max_restart, zero_y=False, exchange=None, frozen=None,
+                record=None):
+        """numpy statement of htn_lanczos_z (same algorithm: CGS2 full reorthogonalisation, eager stop).
+        frozen = Q (nf x n orthonormal rows, or flat): htn_lanczos_orth_z -- the start vector and the Ritz vector are
+        projected (twice), every Gram-Schmidt pass runs over Q followed by the Krylov rows.
+        record = a dict that receives, for the LAST cycle, "alpha" / "beta" (one per step), "basis" (the normalised
+        Lanczos vectors v_0 .. v_k as rows, copied before row 0 is overwritten), and "stop" = (cycle, step) of the end."""
         def matvec(x, y):
             if zero_y:
                 y[...] = 0
@@ -112,6 +117,10 @@ class NumpyOps:
             if exchange is not None:
                 exchange(y)
         kd = krylovdim
+        Q = None if frozen is None else np.asarray(frozen).reshape(-1, n)
+        if Q is not None and len(Q):
+            for _ in range(2):
+                V[0:n] -= Q.T @ (Q.conj() @ V[0:n])
         V[0:n] /= np.linalg.norm(V[0:n])
         nmv, theta, res, beta = 0, 0.0, 0.0, 0.0
         for restart in range(max_restart + 1):
@@ -121,12 +130,15 @@ class NumpyOps:
                 matvec(V[j * n:(j + 1) * n], w)
                 nmv += 1
                 Vm = V[:(j + 1) * n].reshape(j + 1, n)
+                nq = 0
+                if Q is not None and len(Q):
+                    Vm, nq = np.concatenate([Q, Vm]), len(Q)
                 c1 = Vm.conj() @ w
                 w -= Vm.T @ c1
                 c2 = Vm.conj() @ w
                 w -= Vm.T @ c2
                 beta = float(np.linalg.norm(w))
-                alphas.append(float((c1[j] + c2[j]).real))
+                alphas.append(float((c1[nq + j] + c2[nq + j]).real))
                 T = np.diag(alphas) + np.diag(betas, 1) + np.diag(betas, -1)
                 ev, evec = np.linalg.eigh(T)
                 theta, y = float(ev[0]), evec[:, 0]
@@ -137,7 +149,13 @@ class NumpyOps:
                     break
                 betas.append(beta)
             k = len(y)
+            if record is not None:
+                record.update(alpha=list(alphas), beta=list(betas) + [beta], stop=(restart, j),
+                              basis=np.array(V[:(k + 1) * n].reshape(k + 1, n), copy=True))
             x = V[:k * n].reshape(k, n).T @ y.astype(np.complex128)
+            if Q is not None and len(Q):
+                for _ in range(2):
+                    x -= Q.T @ (Q.conj() @ x)
             V[0:n] = x / np.linalg.norm(x)
             if res < tol or beta < 1e-14:
                 break
