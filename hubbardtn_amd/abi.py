@@ -35,7 +35,11 @@ SVD_QRCP = 2
 COPY_DT = np.dtype([("dst_off", "<i8"), ("src_off", "<i8"), ("idx_off", "<i8"), ("scl_off", "<i8"),
                     ("rows", "<i4"), ("cols", "<i4"), ("ldd", "<i4"), ("lds", "<i4"), ("op", "<i4"),
                     ("gather_dim", "<i4"), ("scale_dim", "<i4"), ("inv_norm", "<i4")], align=False)
+QR_DT = np.dtype([("offset", "<i8"), ("m", "<i4"), ("n", "<i4"), ("ld", "<i4"), ("pad", "<i4"), ("r_offset", "<i8"),
+                  ("ldr", "<i4"), ("trans", "<i4")], align=False)
+QR_PANEL, QR_CHUNK, QR_MAX_M = 16, 512, 7664       # HTN_QR_PANEL / HTN_QR_CHUNK / HTN_QR_MAX_M
 assert TILE_DT.itemsize == 64 and SEG_DT.itemsize == 64 and SVD_DT.itemsize == 40 and COPY_DT.itemsize == 64
+assert QR_DT.itemsize == 40
 
 # ---- bond-update / sweep level (ABI 2) ----
 SYM_SU2_U1, SYM_U1_U1, SYM_SU2 = 0, 1, 2
@@ -105,7 +109,9 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_mps_get_site", "htn_mps_env_size", "htn_mps_get_env", "htn_mps_env_blocks", "htn_mps_env_bond",
                   "htn_plan_apply_dump", "htn_mps_cache_stats", "htn_balance_tiles",
                   "htn_idmrg_create", "htn_idmrg_destroy", "htn_idmrg_boundary", "htn_idmrg_step", "htn_idmrg_window",
-                  "htn_mps_set_orthogonal", "htn_mps_orthogonal_count", "htn_mps_overlap"]
+                  "htn_mps_set_orthogonal", "htn_mps_orthogonal_count", "htn_mps_overlap",
+                  "htn_site_update", "htn_dmrg1_sweep", "htn_mps_centre", "htn_mps_site_theta_size", "htn_heff1_apply",
+                  "htn_qr_blocks_z"]
 
 
 class GemmLaunch(C.Structure):
@@ -218,6 +224,13 @@ def declare_engine(lib):
     lib.htn_mps_set_orthogonal.argtypes = [vp, C.POINTER(vp), i32]
     lib.htn_mps_orthogonal_count.argtypes = [vp, C.POINTER(i32)]
     lib.htn_mps_overlap.argtypes = [vp, vp, C.POINTER(f64)]
+    lib.htn_site_update.argtypes = [vp, i32, i32, i32, C.POINTER(SweepOpts), vp]
+    lib.htn_dmrg1_sweep.argtypes = [vp, C.POINTER(SweepOpts), vp, C.POINTER(f64)]
+    lib.htn_mps_centre.argtypes = [vp]
+    lib.htn_mps_site_theta_size.argtypes = [vp, i32]
+    lib.htn_mps_site_theta_size.restype = i64
+    lib.htn_heff1_apply.argtypes = [vp, i32, vp, vp]
+    lib.htn_qr_blocks_z.argtypes = [vp, vp, vp, vp, i32, vp]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

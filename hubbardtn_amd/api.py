@@ -55,6 +55,17 @@ class DMRG2:
 
 
 @dataclass
+class DMRG:
+    """one-site DMRG at the state's current bond tables (MPSKit.DMRG keyword names): converge or polish a state whose
+    bonds two-site sweeps have grown.  tol: on the energy change per site between two sweeps."""
+    tol: float = 1e-6
+    maxiter: int = 100
+    krylovdim: int = 30
+    verbosity: int = 0
+    eigsolve_tol: float = 1e-10
+
+
+@dataclass
 class IDMRG2:
     """infinite two-site DMRG selector (MPSKit.IDMRG2 keyword names; the call at src:1010)"""
     trscheme: object = None
@@ -199,7 +210,8 @@ def initialize_mps(H, P: int, max_dimension: int | None = None, spin: bool = Fal
 def find_groundstate(psi: FiniteMPS, H, alg: DMRG2, envs=None):
     """-> (psi, envs, delta); delta = |E_sweep - E_previous sweep| / L at exit (MPSKit returns the
     last convergence error).  Sweeps until delta < alg.tol or maxiter.  With an InfiniteMPS / IDMRG2: growth steps
-    until the centre Schmidt spectrum changes by less than alg.tol."""
+    until the centre Schmidt spectrum changes by less than alg.tol.  With alg = DMRG(...) on a FiniteMPS: one-site sweeps at
+    the state's current bond tables (engine.DMRG2.sweep1), same return values."""
     if isinstance(psi, InfiniteMPS):
         if not isinstance(alg, IDMRG2) or not isinstance(H, InfiniteHamiltonian):
             raise TypeError("an InfiniteMPS is optimised with IDMRG2 on hamiltonian(simul) without a chain length")
@@ -217,6 +229,20 @@ def find_groundstate(psi: FiniteMPS, H, alg: DMRG2, envs=None):
                                    driver=alg.driver)
         return psi, Environments(psi.result.engine), psi.result.delta
     eng = psi.engine
+    if isinstance(alg, DMRG):
+        # one-site sweeps: the bond tables stay as they are, nothing is truncated
+        eng.krylovdim, eng.lanczos_tol = alg.krylovdim, alg.eigsolve_tol
+        E_prev, delta = None, float("inf")
+        for it in range(alg.maxiter):
+            E = eng.sweep1()
+            if E_prev is not None:
+                delta = abs(E - E_prev) / psi.L
+            if alg.verbosity:
+                print(f"DMRG sweep {it + 1}: E/L = {E / psi.L:.12f}  delta = {delta:.3e}  chi = {max(eng.bond_dims())}")
+            E_prev = E
+            if delta < alg.tol:
+                break
+        return psi, Environments(eng), delta
     if isinstance(alg.trscheme, truncdim):
         eng.chi_full, eng.cutoff = int(alg.trscheme.D), 0.0
     elif isinstance(alg.trscheme, truncbelow):
@@ -496,11 +522,14 @@ def double_occupancy(psi):
     return psi.engine.site_occupations()[1]
 
 
-def TruncState(simul: Simulation, trunc_dim: int, trunc_scheme: int = 0, L: int | None = None, **kw):
+def TruncState(simul: Simulation, trunc_dim: int, trunc_scheme: int = 0, L: int | None = None, polish: str = "twosite", **kw):
     """truncated approximation of the ground state at bond dimension `trunc_dim` (TensorKit dim units), src:1351-1367.
     trunc_scheme 1 = SvdCut (truncate by SVD only); 0 = VUMPSSvdCut (truncate, then re-optimise variationally at
-    that dimension -- here: further two-site sweeps with truncdim(trunc_dim)).  Finite chains (L given) and the infinite
+    that dimension -- here: further two-site sweeps with truncdim(trunc_dim), or, on a finite chain with
+    polish="onesite", one-site sweeps at the bond tables the cut left).  Finite chains (L given) and the infinite
     chain: scheme 1 cuts the bonds of the converged window, scheme 0 = IDMRG2 at truncdim(trunc_dim)."""
+    if polish not in ("twosite", "onesite"):
+        raise ValueError('polish should be either "twosite" or "onesite".')
     if trunc_dim <= 0:
         raise ValueError("trunc_dim should be a positive integer.")
     if trunc_scheme not in (0, 1):
@@ -529,7 +558,7 @@ def TruncState(simul: Simulation, trunc_dim: int, trunc_scheme: int = 0, L: int 
     if trunc_scheme == 0:
         E_prev = None
         for _ in range(kw.get("maxiter", 20)):
-            E = eng.sweep()
+            E = eng.sweep1() if polish == "onesite" else eng.sweep()
             if E_prev is not None and abs(E - E_prev) / psi.L < kw.get("tol", 1e-6):
                 break
             E_prev = E

@@ -291,6 +291,9 @@ struct HipBackend : htn::Backend {
         fork_open = false;
         return rc;
     }
+    int qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks) override {
+        return htn_qr_blocks_z(A, R, desc_dev, desc_host, n_blocks, st);
+    }
     int batched_copy(void* dst, const void* src, const int32_t* idx, const double* scl, const htn_copy_item* items, int n_items,
                      double gscale) override {
         return htn_batched_copy_z(dst, src, idx, scl, items, n_items, gscale, st);

@@ -235,6 +235,14 @@ struct ApplyPlan {
 };
 void plan_apply(const Mpo& mpo, const ThetaLayout& tl, const EnvLayout& Ll, const EnvLayout& Rl, const MpoSite& W1,
                 const MpoSite& W2, ApplyPlan& out);
+// one-site effective Hamiltonian y = GL . W . x . GR for the centre tensor on one site, in the layout `lay` of that site (either
+// kind; the Lanczos vector is the site's stored data).  The inner half of plan_left_env closed with GR: coef_left x
+// (2S_c' + 1) / (2S_c + 1) -- the centre carries sqrt(2S_r + 1) in both layout kinds, as theta does (coef_apply).
+// buffers: BUF_X in, BUF_Y out, BUF_L / BUF_R the environments of the site's bonds, BUF_Z the staging of terms that have both.
+void plan_apply1(const Mpo& mpo, const SiteLayout& lay, const EnvLayout& Ll, const EnvLayout& Rl, const MpoSite& W, ApplyPlan& out);
+// gauge move of a one-site update: QR / LQ descriptors of the centre's sector matrices (left layout: QR, the centre moves
+// right; right layout: LQ, it moves left) and the absorption of the triangular factors (BUF_S1) into the neighbour (BUF_S2 -> BUF_Y)
+void plan_gauge1(const SiteLayout& cen, const SiteLayout& nb, std::vector<htn_qr_block>& desc, int64_t& rsize, Tasks& out);
 void plan_theta(const char* mode, const SiteLayout& lay1, const SiteLayout& lay2, const ThetaLayout& tl, Tasks& out);
 struct EnvPlan {
     Tasks t1, t2;
@@ -329,6 +337,10 @@ struct Backend {
     // Gram-Schmidt (two passes) of the nvec device rows P in place, in order; a row whose remainder falls below drop_tol x its
     // norm is dropped and the rows behind it move up.  -> *kept orthonormal rows.  Default: on the host.
     virtual int orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept);
+    // Unpivoted QR / LQ of strided blocks in place with the orthonormal factor formed (htn_qr_blocks_z in the header).  Default
+    // (htn_engine.cpp): download, Householder reflections on the host, upload -- what the CPU baseline library runs; the HIP
+    // backend overrides it with the kernel.
+    virtual int qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks);
     virtual int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host,
                            int n_blocks, int max_m, int max_sweeps, double tol, int32_t* info_dev,
                            const htn_svd_opts* opts) = 0;
@@ -341,6 +353,9 @@ struct Backend {
     virtual int allreduce(void* y, int64_t n) { return 1; }
     bool timing = false;
 };
+
+// Householder QR / LQ of the blocks on HOST memory, conventions of htn_qr_blocks_z
+void qr_blocks_host(cplx* A, cplx* R, const htn_qr_block* desc, int n_blocks);
 
 int set_error(const char* fmt, ...);        // writes the thread-local error string, returns 1
 char* err_buf();

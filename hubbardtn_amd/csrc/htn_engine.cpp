@@ -193,6 +193,101 @@ int Backend::orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, 
     return 0;
 }
 
+// Householder QR of the blocks on host memory (conventions of htn_qr_blocks_z: R / L diagonal real and non-negative, a column
+// whose remainder is below 1e-13 of its norm gets an exact zero there and no reflector -- Q stays orthonormal by construction)
+void htn::qr_blocks_host(cplx* A, cplx* Rb, const htn_qr_block* desc, int n_blocks) {
+    std::vector<cplx> M, Q, V;
+    std::vector<double> tau, cn;
+    std::vector<cplx> ph;
+    for (int b = 0; b < n_blocks; ++b) {
+        const htn_qr_block& D = desc[b];
+        const int64_t m = D.m, n = D.n;
+        if (m <= 0 || n <= 0) continue;
+        M.assign((size_t)(m * n), cplx(0.0, 0.0));
+        V.assign((size_t)(m * n), cplx(0.0, 0.0));
+        tau.assign((size_t)n, 0.0);
+        cn.assign((size_t)n, 0.0);
+        ph.assign((size_t)n, cplx(1.0, 0.0));
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = 0; i < m; ++i) {
+                M[(size_t)(i + j * m)] = D.trans ? std::conj(A[D.offset + j + i * D.ld]) : A[D.offset + i + j * D.ld];
+                cn[(size_t)j] += std::norm(M[(size_t)(i + j * m)]);
+            }
+        for (int64_t k = 0; k < n; ++k) {
+            double n2 = 0.0;
+            for (int64_t i = k; i < m; ++i) n2 += std::norm(M[(size_t)(i + k * m)]);
+            const double nr = sqrt(n2);
+            if (!(nr > 1e-13 * sqrt(cn[(size_t)k]))) {
+                for (int64_t i = k; i < m; ++i) M[(size_t)(i + k * m)] = cplx(0.0, 0.0);
+                continue;
+            }
+            const cplx x0 = M[(size_t)(k + k * m)];
+            const cplx p = std::abs(x0) > 0.0 ? x0 / std::abs(x0) : cplx(1.0, 0.0);
+            const cplx beta = -p * nr;
+            double vn2 = 0.0;
+            for (int64_t i = k; i < m; ++i) {
+                V[(size_t)(i + k * m)] = M[(size_t)(i + k * m)] - (i == k ? beta : cplx(0.0, 0.0));
+                vn2 += std::norm(V[(size_t)(i + k * m)]);
+            }
+            tau[(size_t)k] = 2.0 / vn2;
+            ph[(size_t)k] = -p;
+            for (int64_t j = k + 1; j < n; ++j) {
+                cplx w(0.0, 0.0);
+                for (int64_t i = k; i < m; ++i) w += std::conj(V[(size_t)(i + k * m)]) * M[(size_t)(i + j * m)];
+                w *= tau[(size_t)k];
+                for (int64_t i = k; i < m; ++i) M[(size_t)(i + j * m)] -= V[(size_t)(i + k * m)] * w;
+            }
+            M[(size_t)(k + k * m)] = beta;
+            for (int64_t i = k + 1; i < m; ++i) M[(size_t)(i + k * m)] = cplx(0.0, 0.0);
+        }
+        Q.assign((size_t)(m * n), cplx(0.0, 0.0));
+        for (int64_t j = 0; j < n; ++j) Q[(size_t)(j + j * m)] = cplx(1.0, 0.0);
+        for (int64_t k = n - 1; k >= 0; --k) {
+            if (tau[(size_t)k] == 0.0) continue;
+            for (int64_t j = 0; j < n; ++j) {
+                cplx w(0.0, 0.0);
+                for (int64_t i = k; i < m; ++i) w += std::conj(V[(size_t)(i + k * m)]) * Q[(size_t)(i + j * m)];
+                w *= tau[(size_t)k];
+                for (int64_t i = k; i < m; ++i) Q[(size_t)(i + j * m)] -= V[(size_t)(i + k * m)] * w;
+            }
+        }
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = 0; i < m; ++i) {
+                const cplx q = Q[(size_t)(i + j * m)] * ph[(size_t)j];
+                if (D.trans) A[D.offset + j + i * D.ld] = std::conj(q);
+                else A[D.offset + i + j * D.ld] = q;
+            }
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = 0; i < n; ++i) {
+                cplx r = i <= j ? M[(size_t)(i + j * m)] * std::conj(ph[(size_t)i]) : cplx(0.0, 0.0);
+                if (i == j) r = cplx(r.real(), 0.0);
+                if (D.trans) Rb[D.r_offset + j + i * D.ldr] = std::conj(r);
+                else Rb[D.r_offset + i + j * D.ldr] = r;
+            }
+    }
+}
+
+int Backend::qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks) {
+    (void)desc_dev;
+    if (n_blocks <= 0) return 0;
+    if (!desc_host) return set_error("qr_blocks: the host copy of the descriptors is required");
+    int64_t a0 = INT64_MAX, a1 = 0, r0 = INT64_MAX, r1 = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        const htn_qr_block& D = desc_host[b];
+        const int64_t vr = D.trans ? D.n : D.m, vc = D.trans ? D.m : D.n;
+        a0 = std::min(a0, D.offset), a1 = std::max(a1, D.offset + (vc - 1) * D.ld + vr);
+        r0 = std::min(r0, D.r_offset), r1 = std::max(r1, D.r_offset + (int64_t)(D.n - 1) * D.ldr + D.n);
+    }
+    std::vector<cplx> ha((size_t)(a1 - a0)), hr((size_t)(r1 - r0));
+    if (download(ha.data(), (cplx*)A + a0, sizeof(cplx) * ha.size()) || download(hr.data(), (cplx*)R + r0, sizeof(cplx) * hr.size()))
+        return 1;
+    std::vector<htn_qr_block> d(desc_host, desc_host + n_blocks);
+    for (auto& D : d) D.offset -= a0, D.r_offset -= r0;
+    qr_blocks_host(ha.data(), hr.data(), d.data(), n_blocks);
+    if (upload((cplx*)A + a0, ha.data(), sizeof(cplx) * ha.size()) || upload((cplx*)R + r0, hr.data(), sizeof(cplx) * hr.size())) return 1;
+    return sync();
+}
+
 // Handles are reference counted: an htn_mps keeps its context and its MPO alive, so destroying the handles in any order
 // (garbage-collected host languages do exactly that) is safe; the last release frees the object.
 struct htn_ctx {
@@ -287,6 +382,16 @@ struct OvlC {                      // compiled overlap transfer / projection (pl
     DevTasks d1, d2;
     int64_t zsize = 0;
 };
+struct RelayC {                    // copy items that re-lay a site tensor from one layout kind to another (or copy it)
+    DBufP items;
+    int n = 0;
+};
+struct Gauge1C {                   // compiled gauge move of a one-site update: QR / LQ descriptors + absorption into the neighbour
+    std::vector<htn_qr_block> desc;
+    DBufP desc_dev;
+    int64_t rsize = 0;
+    DevTasks absorb;
+};
 struct OrthState {                 // one attached state phi: overlap environments <psi|phi> per bond, carried along the sweep
     htn_mps* phi = nullptr;
     std::vector<OvlLayoutP> Llay, Rlay;
@@ -316,6 +421,7 @@ struct htn_mps {
     std::vector<int32_t> idx_host;
     std::vector<OrthState> orth;        // htn_mps_set_orthogonal: the sweep stays in the orthogonal complement of these states
     int orth_dropped = 0;               // projector vectors dropped as numerically dependent in the last bond update
+    int centre = 0;                     // site that carries the centre (htn_mps_create: 0; every update moves it)
 
     template <class T, class F>
     std::shared_ptr<T> cached(const std::string& key, F build) {
@@ -410,6 +516,12 @@ struct htn_mps {
     int theta_into(int i, const ThetaLayout& tl, cplx* dst);
     int update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
     int sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
+    // one-site DMRG (htn_site_update / htn_dmrg1_sweep)
+    std::shared_ptr<ApplyC> make_apply1(int i, const SiteLayout& lay);
+    int heff1_stages(int i, const ApplyC& ap, const DView& z, htn_gemm_launch* stages);
+    int relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst);
+    int update_site(int i, int direction, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
+    int sweep1(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
 };
 
 // GL on bond i+1 from GL on bond i and the left-layout tensor of site i
@@ -894,6 +1006,7 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
     if (o.profile) be->sync();
     const double t_env = now() - t0 - t_plan - t_lan - t_svd;
     energy = E;
+    centre = right ? i + 1 : i;
     Spectrum spec;
     {
         size_t p = 0;
@@ -942,6 +1055,198 @@ int htn_mps::sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E) {
         if (update_bond(i, +1, i < L - 2, true, o, st ? st + k : nullptr)) return 1;
     for (int i = L - 3; i >= 0; --i, ++k)
         if (update_bond(i, -1, false, true, o, st ? st + k : nullptr)) return 1;
+    if (E) *E = energy;
+    return 0;
+}
+
+// =====================================================================================================================
+// One-site DMRG at fixed bond tables (htn_site_update / htn_dmrg1_sweep).  The Lanczos vector is the centre site's stored
+// data; the gauge move is an unpivoted QR (rightwards, left layout: one matrix [(l, s) ; n_r] per right sector) or LQ
+// (leftwards, right layout: [n_l ; (s, r)] per left sector) through Backend::qr_blocks, the triangular factor goes into
+// the neighbour by one grouped GEMM.  No scale factors: in the tilde normalisation left isometries carry 1, the centre
+// sqrt(2S_r + 1) in both layout kinds and right tensors sqrt((2S_r + 1) / (2S_l + 1)), so R (carrying sqrt(2S_c + 1))
+// times B_{i+1} and A_{i-1} times L are centres again and Q is orthonormal in the plain sense.
+// =====================================================================================================================
+std::shared_ptr<ApplyC> htn_mps::make_apply1(int i, const SiteLayout& lay) {
+    return cached<ApplyC>(ikey("apply1", i) + lay.kind + bonds[i]->key + "|" + bonds[i + 1]->key, [&]() -> std::shared_ptr<ApplyC> {
+        ApplyPlan p;
+        plan_apply1(*mpo, lay, *Llay[i], *Rlay[i + 1], mpo->sites[i], p);
+        auto a = std::make_shared<ApplyC>();
+        a->has_z = p.has_z;
+        a->zsize = p.zsize;
+        a->flops = p.ty.flops + (p.has_z ? p.tz.flops : 0);
+        a->ntiles = p.ty.ntiles + (p.has_z ? p.tz.ntiles : 0);
+        a->nsegs = p.ty.nsegs + (p.has_z ? p.tz.nsegs : 0);
+        if (p.has_z && upload_tasks(p.tz, a->dz)) return nullptr;
+        if (upload_tasks(p.ty, a->dy)) return nullptr;
+        return a;
+    });
+}
+
+int htn_mps::heff1_stages(int i, const ApplyC& ap, const DView& z, htn_gemm_launch* stages) {
+    if (ensure_ws(std::max(ap.dy.ws_slots, ap.has_z ? ap.dz.ws_slots : 0))) return -1;
+    memset(stages, 0, 2 * sizeof(htn_gemm_launch));
+    stages[0].bufs[HTN_BUF_WS] = stages[1].bufs[HTN_BUF_WS] = ws.ptr();
+    int ns = 0;
+    if (ap.has_z) {
+        stages[ns].bufs[BUF_L] = Lbuf[i].ptr();
+        stages[ns].bufs[BUF_Z] = z.ptr();
+        stages[ns].tiles = ap.dz.tiles, stages[ns].segs = ap.dz.segs, stages[ns].n_tiles = ap.dz.ntiles;
+        ++ns;
+    }
+    stages[ns].bufs[BUF_L] = Lbuf[i].ptr();
+    stages[ns].bufs[BUF_R] = Rbuf[i + 1].ptr();
+    stages[ns].bufs[BUF_Z] = z.ptr();
+    stages[ns].tiles = ap.dy.tiles, stages[ns].segs = ap.dy.segs, stages[ns].n_tiles = ap.dy.ntiles;
+    return ns + 1;
+}
+
+// dst (layout `to`) = src (layout `from`), block by block: the two kinds hold the same (l, s, r) blocks with the same values
+int htn_mps::relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst) {
+    auto rc = cached<RelayC>(std::string("relay") + from.kind + to.kind + from.bl->key + "|" + from.br->key, [&]() -> std::shared_ptr<RelayC> {
+        std::vector<htn_copy_item> items;
+        for (size_t q = 0; q < to.blocks.size(); ++q) {
+            const Key& k = to.bkeys[q];
+            const int sq = from.block({k[0], k[1]}, k[2], {k[3], k[4]});
+            if (sq < 0) continue;
+            const BlockRec &D = to.blocks[q], &S = from.blocks[sq];
+            htn_copy_item it;
+            memset(&it, 0, sizeof(it));
+            it.dst_off = D.off, it.src_off = S.off, it.idx_off = -1, it.scl_off = -1;
+            it.rows = D.m, it.cols = D.n, it.ldd = D.ld, it.lds = S.ld;
+            it.op = HTN_OP_N, it.gather_dim = 0, it.scale_dim = -1, it.inv_norm = 0;
+            items.push_back(it);
+        }
+        auto r = std::make_shared<RelayC>();
+        r->n = (int)items.size();
+        r->items = dalloc(sizeof(htn_copy_item) * std::max<size_t>(items.size(), 1));
+        if (!r->items || be->upload(r->items->p, items.data(), sizeof(htn_copy_item) * items.size())) return nullptr;
+        return r;
+    });
+    if (!rc) return 1;
+    return rc->n ? be->batched_copy(dst, src, nullptr, nullptr, (const htn_copy_item*)rc->items->p, rc->n, 1.0) : 0;
+}
+
+static int site1_checks(const htn_mps* m, int i, const char* who) {
+    if (i < 0 || i >= m->L) return set_error("%s: site %d out of range", who, i);
+    if (m->centre != i) return set_error("%s: the centre is on site %d, not on site %d", who, m->centre, i);
+    if (!m->orth.empty()) return set_error("%s: one-site updates of a state with attached orthogonal states are not supported", who);
+    if (m->ctx->world > 1 || m->ctx->shard || m->be->has_comm())
+        return set_error("%s: one-site updates on a context with a communicator are not supported", who);
+    if (!m->Llay[i] || !m->Rlay[i + 1] || m->Llay[i]->bond->key != m->bonds[i]->key || m->Rlay[i + 1]->bond->key != m->bonds[i + 1]->key)
+        return set_error("%s: the environments of site %d were built on other bond tables: run a two-site sweep first", who, i);
+    return 0;
+}
+
+int htn_mps::update_site(int i, int direction, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st) {
+    if (site1_checks(this, i, "htn_site_update")) return 1;
+    if (direction < -1 || direction > 1) return set_error("htn_site_update: direction %d (must be -1, 0 or +1)", direction);
+    if ((direction > 0 && i + 1 >= L) || (direction < 0 && i == 0))
+        return set_error("htn_site_update: site %d has no neighbour in direction %d", i, direction);
+    const double t0 = now();
+    const Sym& sym = mpo->sym;
+    const SiteLayoutP cur = site_lay[i];
+    const SiteLayoutP lay = direction == 0 ? cur : site_layout(direction > 0 ? 'L' : 'R', bonds[i], bonds[i + 1]);
+    const int64_t n = lay->size;
+    if (n <= 0) return set_error("htn_site_update: empty site tensor on site %d", i);
+    for (const auto& M : lay->mats)      // a full-rank gauge move needs the long side along the orthonormal direction
+        if (direction != 0 && (lay->kind == 'L' ? M.rows < M.cols : M.cols < M.rows))
+            return set_error("htn_site_update: sector (%d, %d) of site %d is a %d x %d block, its bond is wider than the rest of the "
+                             "site supports: run a two-site sweep first", M.c.N, M.c.j, i, M.rows, M.cols);
+    if (direction != 0 && site_lay[i + direction]->kind != (direction > 0 ? 'R' : 'L'))
+        return set_error("htn_site_update: site %d is not in %s layout", i + direction, direction > 0 ? "right" : "left");
+    const int kd = o.krylovdim > 0 ? o.krylovdim : 30;
+    DView V = zalloc((int64_t)(kd + 2) * n, false);
+    if (!V.base) return set_error("device allocation of the Krylov basis failed (%lld elements)", (long long)((kd + 2) * n));
+    if (relay(*cur, site_buf[i].ptr(), *lay, V.ptr())) return 1;
+    auto ap = make_apply1(i, *lay);
+    if (!ap) return 1;
+    DView z = zalloc(ap->zsize, false);
+    if (!z.base) return set_error("device allocation failed (one-site apply)");
+    htn_gemm_launch stages[2];
+    const int ns = heff1_stages(i, *ap, z, stages);
+    if (ns < 0) return 1;
+    if (o.profile) be->sync();
+    const double t_plan = now() - t0;
+    double E = 0.0, res = 0.0, mv_ms = 0.0;
+    int nmv = 0;
+    if (be->lanczos(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, 0, nullptr, ctx, &E, &nmv,
+                    &res, be->timing ? &mv_ms : nullptr))
+        return 1;
+    if (o.profile) be->sync();
+    const double t_lan = now() - t0 - t_plan;
+    // ---- the optimised centre, then the gauge move ----
+    DView out = zalloc(n, false);
+    if (!out.base) return set_error("device allocation failed (site tensor)");
+    if (relay(*lay, V.ptr(), *lay, out.ptr())) return 1;
+    double t_env = 0.0;
+    const int crossed = direction > 0 ? i + 1 : i;
+    if (direction != 0) {
+        const int j = i + direction;
+        const SiteLayoutP nl = site_lay[j];
+        auto gc = cached<Gauge1C>(std::string(direction > 0 ? "gauge1R" : "gauge1L") + lay->bl->key + "|" + lay->br->key + "|" +
+                                      (direction > 0 ? nl->br->key : nl->bl->key),
+                                  [&]() -> std::shared_ptr<Gauge1C> {
+                                      auto g = std::make_shared<Gauge1C>();
+                                      Tasks t;
+                                      plan_gauge1(*lay, *nl, g->desc, g->rsize, t);
+                                      g->desc_dev = dalloc(sizeof(htn_qr_block) * std::max<size_t>(g->desc.size(), 1));
+                                      if (!g->desc_dev || be->upload(g->desc_dev->p, g->desc.data(), sizeof(htn_qr_block) * g->desc.size()))
+                                          return nullptr;
+                                      if (upload_tasks(t, g->absorb)) return nullptr;
+                                      return g;
+                                  });
+        if (!gc) return 1;
+        DView Rf = zalloc(gc->rsize, false), nb_out = zalloc(nl->size, false);
+        if (!Rf.base || !nb_out.base) return set_error("device allocation failed (gauge move)");
+        if (be->qr_blocks(out.ptr(), Rf.ptr(), (const htn_qr_block*)gc->desc_dev->p, gc->desc.data(), (int)gc->desc.size())) return 1;
+        if (gemm(gc->absorb, {{BUF_S1, Rf.ptr()}, {BUF_S2, site_buf[j].ptr()}, {BUF_Y, nb_out.ptr()}})) return 1;
+        site_lay[i] = lay;
+        site_buf[i] = out;
+        site_buf[j] = nb_out;
+        centre = j;
+        if (o.profile) be->sync();
+        const double t1 = now();
+        if (direction > 0 ? left_env(i) : right_env(i)) return 1;
+        if (o.profile) be->sync();
+        t_env = now() - t1;
+    } else {
+        site_lay[i] = lay;
+        site_buf[i] = out;
+    }
+    energy = E;
+    if (st) {
+        memset(st, 0, sizeof(*st));
+        st->bond = crossed;
+        st->direction = direction;
+        st->n_matvec = nmv;
+        st->chi_full = (int32_t)bonds[crossed]->dim_full(sym);
+        st->multiplets = bonds[crossed]->multiplets();
+        st->n_tiles = ap->ntiles;
+        st->n_segs = ap->nsegs;
+        st->theta_size = n;
+        st->apply_flops = ap->flops;
+        st->apply_bytes = 16 * (2 * n + Llay[i]->size + Rlay[i + 1]->size);
+        st->energy = E;
+        st->residual = res;
+        st->t_plan = t_plan;
+        st->t_lanczos = t_lan;
+        st->t_env = t_env;
+        st->t_total = now() - t0;
+        st->t_svd = st->t_total - t_plan - t_lan - t_env;       // the QR / LQ and the absorption
+        st->matvec_ms = mv_ms > 0.0 ? mv_ms : 0.0;
+    }
+    return 0;
+}
+
+int htn_mps::sweep1(const htn_sweep_opts& o, htn_bond_stats* st, double* E) {
+    if (L < 2) return set_error("htn_dmrg1_sweep: a chain of %d site(s) has no bond to sweep over", L);
+    if (centre != 0) return set_error("htn_dmrg1_sweep: the centre is on site %d, not on site 0", centre);
+    int k = 0;
+    for (int i = 0; i < L - 1; ++i, ++k)
+        if (update_site(i, +1, true, o, st ? st + k : nullptr)) return 1;
+    for (int i = L - 1; i >= 1; --i, ++k)
+        if (update_site(i, -1, true, o, st ? st + k : nullptr)) return 1;
     if (E) *E = energy;
     return 0;
 }
@@ -1744,6 +2049,52 @@ int htn_bond_update(htn_mps* mps, int32_t i, int32_t direction, int32_t placemen
 int htn_dmrg2_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* stats, double* energy) {
     if (mps->be->activate()) return 1;
     return mps->sweep(norm_opts(opts), stats, energy);
+}
+
+int htn_site_update(htn_mps* mps, int32_t i, int32_t direction, int32_t optimise, const htn_sweep_opts* opts, htn_bond_stats* stats) {
+    if (!mps) return set_error("htn_site_update: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->update_site(i, direction, optimise != 0, norm_opts(opts), stats);
+}
+int htn_dmrg1_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* stats, double* energy) {
+    if (!mps) return set_error("htn_dmrg1_sweep: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->sweep1(norm_opts(opts), stats, energy);
+}
+int32_t htn_mps_centre(const htn_mps* mps) { return mps->centre; }
+int64_t htn_mps_site_theta_size(htn_mps* mps, int32_t i) {
+    if (i < 0 || i >= mps->L) return -1;
+    return mps->site_lay[i]->size;
+}
+int htn_heff1_apply(htn_mps* mps, int32_t i, const void* x_host, void* y_host) {
+    if (!mps || !x_host || !y_host) return set_error("htn_heff1_apply: bad arguments");
+    if (site1_checks(mps, i, "htn_heff1_apply")) return 1;
+    if (mps->be->activate()) return 1;
+    const SiteLayout& lay = *mps->site_lay[i];
+    auto ap = mps->make_apply1(i, lay);
+    if (!ap) return 1;
+    const int64_t n = lay.size;
+    DView x = mps->zalloc(n, false), y = mps->zalloc(n, true), z = mps->zalloc(ap->zsize, false);
+    if (!x.base || !y.base || !z.base) return set_error("device allocation failed");
+    if (mps->be->upload(x.ptr(), x_host, sizeof(cplx) * n)) return 1;
+    if (ap->has_z && mps->gemm(ap->dz, {{BUF_X, x.ptr()}, {BUF_L, mps->Lbuf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (mps->gemm(ap->dy, {{BUF_X, x.ptr()}, {BUF_Y, y.ptr()}, {BUF_L, mps->Lbuf[i].ptr()}, {BUF_R, mps->Rbuf[i + 1].ptr()}, {BUF_Z, z.ptr()}}))
+        return 1;
+    return mps->be->download(y_host, y.ptr(), sizeof(cplx) * n);
+}
+// Host-memory statement of the kernel-level entry (Householder reflections): what the CPU baseline library exports.  Weak: in
+// libhubbardtn_hip.so the definition of htn_qr.hip (device pointers, the gfx950 kernel) takes its place at link time.
+__attribute__((weak)) int htn_qr_blocks_z(void* A, void* Rbuf, const htn_qr_block* desc, const htn_qr_block* desc_host, int32_t n_blocks,
+                                          void* stream) {
+    (void)stream;
+    if (n_blocks <= 0) return 0;
+    if (!A || !Rbuf || (!desc && !desc_host)) return set_error("htn_qr_blocks_z: bad arguments");
+    const htn_qr_block* d = desc_host ? desc_host : desc;
+    for (int b = 0; b < n_blocks; ++b)
+        if (d[b].n < 1 || d[b].m < d[b].n || d[b].ldr < d[b].n || d[b].ld < (d[b].trans ? d[b].n : d[b].m))
+            return set_error("htn_qr_blocks_z: block %d: m = %d, n = %d, ld = %d, ldr = %d (need m >= n >= 1)", b, d[b].m, d[b].n, d[b].ld, d[b].ldr);
+    qr_blocks_host((cplx*)A, (cplx*)Rbuf, d, n_blocks);
+    return 0;
 }
 
 int htn_mps_set_orthogonal(htn_mps* mps, const htn_mps* const* others, int32_t n) {

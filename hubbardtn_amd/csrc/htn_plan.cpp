@@ -855,6 +855,119 @@ void plan_apply(const Mpo& mpo, const ThetaLayout& tl, const EnvLayout& Ll, cons
     out.nterms = nterms;
 }
 
+// ---- y = H_eff x for ONE site (one-site DMRG) ------------------------------------------------------------------------
+// y[a',s',c'] += coef * L[a',w,a] x[a,s,c] R[c,w',c'] with coef = coef_left(site) * (2S_c' + 1) / (2S_c + 1): the left half is
+// stage 1 of plan_left_env, the closing factor the one coef_apply carries for the right bond of theta.  Terms with both
+// environments go through BUF_Z (Z = L x, summed over a, w and s for one (output block, w', c)), like plan_apply.
+void plan_apply1(const Mpo& mpo, const SiteLayout& lay, const EnvLayout& Ll, const EnvLayout& Rl, const MpoSite& W, ApplyPlan& out) {
+    const Sym& sym = mpo.sym;
+    const int nfin = (int)W.right.size() - 1;
+    TaskList ty, tz;
+    for (size_t i = 0; i < lay.blocks.size(); ++i) {
+        const BlockRec& r = lay.blocks[i];
+        ty.block(lay.bkeys[i], BUF_Y, r.off, r.m, r.n, r.ld);
+    }
+    int64_t zoff = 0, nterms = 0;
+    KeyMap zblocks;
+    for (size_t xi = 0; xi < lay.blocks.size(); ++xi) {
+        const Key& beta = lay.bkeys[xi];
+        const BlockRec& X = lay.blocks[xi];
+        const Sec a{beta[0], beta[1]}, c{beta[3], beta[4]};
+        const int s = beta[2];
+        for (auto& e : W.entries) {
+            const int w = e.wl, wp = e.wr;
+            const SiteOp& o = mpo.ops[e.op];
+            const int kl = W.left[w].k, kr = W.right[wp].k;
+            std::vector<Sec> one_a{a}, one_c{c};
+            const std::vector<Sec>* aps = w == 0 ? &one_a : Ll.kets(w, a);
+            const std::vector<Sec>* cps = wp == nfin ? &one_c : Rl.kets(wp, c);
+            if (!aps || !cps) continue;
+            for (int sp = 0; sp < sym.n_site; ++sp) {
+                const double r = o.red[sp][s];
+                if (r == 0.0) continue;
+                for (Sec ap : *aps)
+                    for (Sec cp : *cps) {
+                        const int oi = ty.find(mk(ap.N, ap.j, sp, cp.N, cp.j));
+                        if (oi < 0) continue;
+                        const double cf = coef_left(sym.jeff(ap.j), sym.jeff(kl), sym.jeff(a.j), sym.jeff(sym.site[sp].j),
+                                                    sym.jeff(sym.site[s].j), sym.jeff(o.k), sym.jeff(cp.j), sym.jeff(kr),
+                                                    sym.jeff(c.j)) *
+                                          (sym.jeff(cp.j) + 1) / (sym.jeff(c.j) + 1);
+                        const cplx alpha = cf * r * e.coef;
+                        if (alpha == cplx(0.0, 0.0)) continue;
+                        ++nterms;
+                        const bool hasL = w != 0, hasR = wp != nfin;
+                        if (!hasL && !hasR) {
+                            ty.copy(oi, BUF_X, X.off, X.ld, alpha);
+                        } else if (hasL && !hasR) {
+                            const auto& Lb = Ll.blocks[Ll.block(ap, w, a)];
+                            ty.gemm(oi, BUF_L, Lb.off, Lb.m, HTN_OP_N, BUF_X, X.off, X.ld, HTN_OP_N, Lb.n, alpha);
+                        } else if (hasR && !hasL) {
+                            const auto& Rb = Rl.blocks[Rl.block(c, wp, cp)];
+                            ty.gemm(oi, BUF_X, X.off, X.ld, HTN_OP_N, BUF_R, Rb.off, Rb.m, HTN_OP_N, Rb.m, alpha);
+                        } else {
+                            const auto& Lb = Ll.blocks[Ll.block(ap, w, a)];
+                            const auto& Rb = Rl.blocks[Rl.block(c, wp, cp)];
+                            const Key zk = mk(oi, wp, c.N, c.j);
+                            int zi;
+                            auto iz = zblocks.find(zk);
+                            if (iz == zblocks.end()) {
+                                zi = tz.block(zk, BUF_Z, zoff, Lb.m, X.n, Lb.m);
+                                zblocks[zk] = zi;
+                                ty.gemm(oi, BUF_Z, zoff, Lb.m, HTN_OP_N, BUF_R, Rb.off, Rb.m, HTN_OP_N, Rb.m, 1.0);
+                                zoff += (int64_t)Lb.m * X.n;
+                            } else
+                                zi = iz->second;
+                            tz.gemm(zi, BUF_L, Lb.off, Lb.m, HTN_OP_N, BUF_X, X.off, X.ld, HTN_OP_N, Lb.n, alpha);
+                        }
+                    }
+            }
+        }
+    }
+    out.has_z = !zblocks.empty();
+    if (out.has_z) tz.finalize(out.tz);
+    ty.finalize(out.ty);
+    for (const auto& M : lay.mats) out.ty.group_bounds.push_back(M.off);      // placement hint: one group per sector matrix of y
+    out.zsize = zoff;
+    out.nterms = nterms;
+}
+
+// ---- gauge move of a one-site update -----------------------------------------------------------------------------------
+// QR (centre in left layout, move right) or LQ (right layout, move left) descriptors of the centre's sector matrices, and
+// the task list that takes the triangular factors (BUF_S1, one n_c x n_c matrix per sector, ld n_c) into the neighbour
+// (BUF_S2 -> BUF_Y, same layout): B_c <- R_c B_c per left sector c of a right-layout neighbour, A_c <- A_c L_c per right
+// sector of a left-layout one.  A sector the centre does not reach has no segment: its block is written as zeros.
+void plan_gauge1(const SiteLayout& cen, const SiteLayout& nb, std::vector<htn_qr_block>& desc, int64_t& rsize, Tasks& out) {
+    const bool right = cen.kind == 'L';
+    desc.clear();
+    rsize = 0;
+    std::unordered_map<uint64_t, std::pair<int64_t, int>> rof;
+    for (const auto& M : cen.mats) {
+        htn_qr_block d;
+        memset(&d, 0, sizeof(d));
+        d.offset = M.off;
+        d.ld = M.rows;
+        d.trans = right ? 0 : 1;
+        d.m = right ? M.rows : M.cols;
+        d.n = right ? M.cols : M.rows;
+        d.r_offset = rsize;
+        d.ldr = d.n;
+        rof[skey(M.c)] = {rsize, d.n};
+        rsize += (int64_t)d.n * d.n;
+        desc.push_back(d);
+    }
+    TaskList t;
+    for (const auto& M : nb.mats) {
+        const int bi = t.block(mk(M.c.N, M.c.j), BUF_Y, M.off, M.rows, M.cols, M.rows);
+        auto it = rof.find(skey(M.c));
+        if (it == rof.end()) continue;
+        const int nc = it->second.second;
+        if (right) t.gemm(bi, BUF_S1, it->second.first, nc, HTN_OP_N, BUF_S2, M.off, M.rows, HTN_OP_N, nc, 1.0);
+        else t.gemm(bi, BUF_S2, M.off, M.rows, HTN_OP_N, BUF_S1, it->second.first, nc, HTN_OP_N, nc, 1.0);
+    }
+    t.finalize(out);
+}
+
 // ---- theta = T1 . T2 ------------------------------------------------------------------------------------------------
 // mode "RR": both right layout (centre on i); "LL": both left layout (centre on i+1); "LR": left x right layout.
 // buffers: BUF_S1 = site i, BUF_S2 = site i+1, output BUF_Y.

@@ -283,6 +283,12 @@ class HipOps:
                                                       C.byref(opts), self._stream()), "htn_jacobi_svd_z")
         return used.value
 
+    def qr_blocks(self, A, R, desc_dev, desc_host, nblocks):
+        """htn_qr_blocks_z: unpivoted QR / LQ of the strided blocks of A in place, triangular factors into R (abi.QR_DT)"""
+        desc_host = np.ascontiguousarray(desc_host)
+        abi.check(self.lib, self.lib.htn_qr_blocks_z(self._p(A), self._p(R), self._p(desc_dev), desc_host.ctypes.data, nblocks,
+                                                     self._stream()), "htn_qr_blocks_z")
+
     def batched_copy(self, dst, src, idx, scl, items_dev, nitems, gscale):
         if nitems == 0:
             return

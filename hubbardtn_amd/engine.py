@@ -416,6 +416,59 @@ class DMRG2:
         self.energy = E.value
         return self.energy
 
+    # ---- one-site DMRG at fixed bond tables (htn_site_update / htn_dmrg1_sweep) --------------------
+    def centre(self) -> int:
+        """the site that carries the centre (0 after construction and after every sweep)"""
+        return int(self.lib.htn_mps_centre(self.handle))
+
+    def update_site(self, i, direction, optimise=True, record=True):
+        """one-site update of site i (the centre must be there): lowest eigenpair of the one-site effective Hamiltonian
+        (optimise=False: <x|H_eff|x> only), then direction +1: QR, site i becomes a left isometry, the centre moves to
+        i + 1; -1: LQ, the centre moves to i - 1; 0: it stays.  Bond tables never change.  Returns the eigenvalue, which
+        is <psi|H|psi> of the stored state (nothing is truncated)."""
+        self.__dict__.pop("_bond_cache", None)
+        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
+        o = self._opts()
+        self._check(self.lib.htn_site_update(self.handle, i, direction, 1 if optimise else 0, C.byref(o), st.ctypes.data),
+                    "htn_site_update")
+        s = _stats(st[0])
+        if record:
+            self.stats.append(s)
+            self.energy = s.energy
+        return s.energy
+
+    def sweep1(self):
+        """one one-site sweep at the current bond tables (sites 0..L-2 rightwards, L-1..1 leftwards, 2L-2 updates, one
+        library call); the centre ends on site 0.  Grow the bonds with sweep() first.  The Schmidt spectra
+        (`spectrum`) keep the values of the last two-site update of each bond."""
+        self.__dict__.pop("_bond_cache", None)
+        n = 2 * self.L - 2
+        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
+        E = C.c_double(0.0)
+        o = self._opts()
+        self._check(self.lib.htn_dmrg1_sweep(self.handle, C.byref(o), st.ctypes.data, C.byref(E)), "htn_dmrg1_sweep")
+        self.stats.extend(_stats(r) for r in st)
+        self.energy = E.value
+        return self.energy
+
+    def apply_heff1(self, i, x):
+        """y = H_eff(site i) x on host vectors in the stored layout of site i (the flat vector of `download_site`'s
+        blocks: htn_mps_get_site); the centre must be on site i"""
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        n = self.lib.htn_mps_site_theta_size(self.handle, i)
+        assert x.shape == (n,)
+        y = np.zeros(n, dtype=np.complex128)
+        self._check(self.lib.htn_heff1_apply(self.handle, i, x.ctypes.data, y.ctypes.data), "htn_heff1_apply")
+        return y
+
+    def site_vector(self, i):
+        """the stored data of site i as one flat vector (the Lanczos vector of a one-site update when i is the centre)"""
+        n = self.lib.htn_mps_site_size(self.handle, i, None)
+        flat = np.zeros(max(n, 1), dtype=np.complex128)
+        if self.lib.htn_mps_get_site(self.handle, i, None, flat.ctypes.data) < 0:
+            raise abi.HtnError(self.lib.htn_last_error().decode())
+        return flat[:n]
+
     def site_probabilities(self):
         """-> P[L, n_site]: probability of every site multiplet on every site.  Call after sweep() (centre on site 0,
         sites >= 1 right-canonical).  The centre is carried through the chain without optimisation; with the centre on

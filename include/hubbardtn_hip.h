@@ -230,6 +230,38 @@ int htn_batched_copy_z(void* dst, const void* src, const int32_t* idx, const dou
                        const htn_copy_item* items, int32_t n_items, double global_scale,
                        void* stream);
 
+/* Batched unpivoted QR / LQ that FORMS the orthonormal factor: the gauge move of a one-site update (no pivoting, no
+ * truncation).  Stands in for: TensorKit leftorth! / rightorth! (alg = QRpos / LQpos) per coupled sector as MPSKit's
+ * one-site DMRG() calls them after each site update.
+ * Block i is a strided view inside A, factorised IN PLACE (no staging copy):
+ *   trans = 0 : the m x n view (m >= n, leading dimension ld) at A + offset is overwritten by Q (m x n, orthonormal
+ *               columns); R (n x n upper triangular, strict lower part written as zeros) goes to Rbuf + r_offset, ld ldr.
+ *   trans = 1 : the view is n x m (n rows, m >= n columns, leading dimension ld); its conjugate transpose is factorised,
+ *               i.e. view = L Qr: the row-orthonormal factor Qr (n x m) goes in place, L (n x n lower triangular, strict
+ *               upper part written as zeros) to Rbuf + r_offset.
+ * Sign rule: the diagonal of R (of L) is real and non-negative.  A column whose remainder after projecting out the
+ * columns before it falls below 1e-13 of its own norm is treated as dependent: its diagonal entry (and the rest of its
+ * remainder) is an exact zero and Q is completed by a unit vector orthogonal to everything before it, so Q always has
+ * orthonormal columns and Q R reproduces the view to rounding.
+ * Method (HIP): left-looking, panels of HTN_QR_PANEL columns held in LDS; a panel is projected against the finished
+ * columns (W = Q^H A_p, A_p -= Q W on v_mfma_f64_16x16x4_f64, Q read back through the L2) -- a second time when a column
+ * lost more than half of its squared norm in the first projection --, then orthonormalised by Gram-Schmidt, always twice.  One workgroup per block, no workgroup waits for another; all sums are taken
+ * in a fixed order, so the result is bit-reproducible.  m is limited by the LDS panel: m <= HTN_QR_MAX_M.
+ * The CPU baseline library exports the same entry on host memory (Householder reflections, same conventions).
+ * desc: device array; desc_host: the same array in host memory (needed: it sizes the launch). */
+#define HTN_QR_PANEL 16          /* panel width while a panel of m rows fits the LDS (m <= 464); halved beyond, down to 1 */
+#define HTN_QR_CHUNK 512         /* rows covered by one pass of the workgroup's row-owning loops (one row per thread)   */
+#define HTN_QR_MAX_M 7664
+typedef struct {
+    int64_t offset;              /* element offset of the view inside A                   */
+    int32_t m, n;                /* long and short extent, m >= n >= 1                    */
+    int32_t ld, pad;
+    int64_t r_offset;            /* element offset of R (L) inside Rbuf                   */
+    int32_t ldr, trans;
+} htn_qr_block;         /* 40 bytes */
+int htn_qr_blocks_z(void* A, void* Rbuf, const htn_qr_block* desc, const htn_qr_block* desc_host, int32_t n_blocks,
+                    void* stream);
+
 
 /* =====================================================================================================
  * Bond-update / sweep level (ABI 2): what sits behind
@@ -375,6 +407,30 @@ int htn_bond_update(htn_mps* mps, int32_t i, int32_t direction, int32_t placemen
 /* one sweep in MPSKit's DMRG2 order: bonds 1..L-1 rightwards, L-2..1 leftwards (2L-3 updates);
  * stats_host: 2L-3 records or NULL; energy_host receives the last eigenvalue */
 int htn_dmrg2_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* stats_host, double* energy_host);
+
+/* One-site DMRG at FIXED bond tables (MPSKit's DMRG(); the "re-optimise variationally at that dimension" step of
+ * TruncState scheme 0, src:1351-1367): grow the bonds with two-site sweeps, converge with these.
+ * htn_site_update: the centre must be on site i (htn_mps_centre).  optimise = 1: lowest eigenpair of the one-site
+ * effective Hamiltonian GL W_i GR by htn_lanczos_z, the Lanczos vector being the site's stored data (re-laid to left
+ * layout for direction +1, to right layout for -1); optimise = 0: <x|H_eff|x> only.  direction +1: QR per right sector
+ * (htn_qr_blocks_z), site i becomes the left isometry Q, site i+1 <- R B_{i+1}, the left environment moves; -1: LQ per
+ * left sector, A_{i-1} <- A_{i-1} L, the right environment moves; 0: the centre stays.  Bond tables never change; a
+ * sector block with fewer rows than columns (possible only in a state no two-site sweep has shaped) is an error that
+ * says "run a two-site sweep first".  Nothing is truncated, so the eigenvalue IS <psi|H|psi> of the stored state.
+ * stats (may be NULL): bond = the bond crossed, t_svd = the QR + absorption, jacobi_sweeps = trunc_weight = 0.
+ * htn_mps_spectrum keeps the Schmidt values of the last TWO-SITE update of a bond: one-site updates do not refresh it.
+ * Refused (not verified): states with attached orthogonal states, contexts with a communicator or an exchange hook.
+ * htn_dmrg1_sweep: sites 0..L-2 rightwards, then L-1..1 leftwards (2L-2 updates, stats_host: 2L-2 records or NULL);
+ * the centre ends on site 0, the convention every other call expects after a sweep; energy_host: the last eigenvalue. */
+int htn_site_update(htn_mps* mps, int32_t i, int32_t direction, int32_t optimise, const htn_sweep_opts* opts,
+                    htn_bond_stats* stats_host);
+int htn_dmrg1_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* stats_host, double* energy_host);
+/* site that carries the centre (0 after htn_mps_create and after every sweep) */
+int32_t htn_mps_centre(const htn_mps* mps);
+/* y = H_eff(site i) x on host vectors in the stored layout of site i (size htn_mps_site_theta_size = htn_mps_site_size;
+ * sub-block table: htn_mps_get_site); the centre must be on site i.  Tests and Hermiticity checks. */
+int64_t htn_mps_site_theta_size(htn_mps* mps, int32_t i);
+int htn_heff1_apply(htn_mps* mps, int32_t i, const void* x_host, void* y_host);
 
 /* Excited states inside one sector: orthogonalised two-site DMRG.  After htn_mps_set_orthogonal(mps, others, n) every
  * OPTIMISING bond update of `mps` finds the lowest eigenpair of H_eff inside the orthogonal complement of the n attached

@@ -257,7 +257,18 @@ struct HIPDMRG2{T} <: MPSKit.Algorithm
 end
 HIPDMRG2(; trscheme, tol = 1e-6, maxiter = 100, krylovdim = 30, P = 1, Q = 1) = HIPDMRG2(trscheme, tol, maxiter, krylovdim, P, Q)
 
-function MPSKit.find_groundstate(ψ::FiniteMPS, H, alg::HIPDMRG2, envs = nothing)
+# one-site DMRG at the bond tables ψ arrives with (MPSKit.DMRG's role): htn_dmrg1_sweep until the energy per site moves by
+# less than tol.  Nothing is truncated; grow the bonds with HIPDMRG2 first.
+struct HIPDMRG <: MPSKit.Algorithm
+    tol::Float64
+    maxiter::Int
+    krylovdim::Int
+    P::Int
+    Q::Int
+end
+HIPDMRG(; tol = 1e-6, maxiter = 100, krylovdim = 30, P = 1, Q = 1) = HIPDMRG(tol, maxiter, krylovdim, P, Q)
+
+function MPSKit.find_groundstate(ψ::FiniteMPS, H, alg::Union{HIPDMRG2, HIPDMRG}, envs = nothing)
     ctx, mpo, mps = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:htn_ctx_create, lib), Cint, (Int32, Int32, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), 1, 0, C_NULL, ctx))     # HTN_BACKEND_HIP, device 0
     try
@@ -270,10 +281,15 @@ function MPSKit.find_groundstate(ψ::FiniteMPS, H, alg::HIPDMRG2, envs = nothing
             (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{HtnSector}, Ptr{Int32}, Ptr{HtnSubblock}, Ptr{Int64}, Ptr{ComplexF64},
              Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
             ctx[], mpo[], length(ψ), bond_ptr, sectors_, sub_ptr, subs, data_ptr, data, C_NULL, C_NULL, mps))
-        opts = sweep_opts(alg.trscheme; krylovdim = alg.krylovdim)
+        onesite = alg isa HIPDMRG
+        opts = sweep_opts(onesite ? TensorKit.NoTruncation() : alg.trscheme; krylovdim = alg.krylovdim)
         E, Eprev, δ = Ref{Float64}(0.0), Inf, Inf
         for it in 1:alg.maxiter
-            check(ccall((:htn_dmrg2_sweep, lib), Cint, (Ptr{Cvoid}, Ref{HtnSweepOpts}, Ptr{Cvoid}, Ref{Float64}), mps[], opts, C_NULL, E))
+            if onesite
+                check(ccall((:htn_dmrg1_sweep, lib), Cint, (Ptr{Cvoid}, Ref{HtnSweepOpts}, Ptr{Cvoid}, Ref{Float64}), mps[], opts, C_NULL, E))
+            else
+                check(ccall((:htn_dmrg2_sweep, lib), Cint, (Ptr{Cvoid}, Ref{HtnSweepOpts}, Ptr{Cvoid}, Ref{Float64}), mps[], opts, C_NULL, E))
+            end
             δ = abs(E[] - Eprev) / length(ψ)
             Eprev = E[]
             δ < alg.tol && break
