@@ -1949,6 +1949,81 @@ __device__ __forceinline__ void ring_recv(double2* dst, const double2* slot, int
     put(tid + 8 * RING_THREADS, u8);
 }
 
+// ---- the direct exchange (default; HTN_RING_STAGED_SEND=1 keeps ring_send / ring_recv above) ---------------------------
+// Same protocol, same slots, same bits; what the staged form did for nothing is gone:
+//   send     the last cross step of a round stores the columns it holds in registers straight to the neighbour's slot
+//            (ring_cross, SEND) -- no LDS round trip, no copy loop, no barrier of its own;
+//   receive  the two directions are independent: waves 0-3 take the top panel, waves 4-7 the bottom one (a workgroup at an
+//            end of the ring receives one panel with all waves), one lane per direction polls, the others of that half watch
+//            a word in LDS, and the loads of a half start when ITS flag is up;
+//   norms    a half loads in the layout of the rotations (a group of GS lanes per column, lane sub holds rows sub + GS e), so
+//            the squared column norms the next round starts from are summed from the registers on their way to LDS -- same
+//            lanes, same element order, same reduction as the recomputation in ring_cross, hence the same bits.
+// One column of E register elements, times its scale, to column offset `off` of a mailbox slot (16-byte stores, sc1 unless
+// `local`, see ring_send).  ALL E elements go out: rows m .. mp - 1 of a panel are zeros in registers as they are in LDS, and
+// they arrive as zeros.
+__device__ __forceinline__ void ring_store16(double2 x, __amdgpu_buffer_rsrc_t rs, int elem, bool local) {
+    ring_u4 u;
+    __builtin_memcpy(&u, &x, 16);
+    if (local) __builtin_amdgcn_raw_buffer_store_b128(u, rs, elem * 16, 0, 0);
+    else __builtin_amdgcn_raw_buffer_store_b128(u, rs, elem * 16, 0, 16);          // aux 16 = sc1
+}
+template <int GS, int E>
+__device__ __forceinline__ void ring_send_col(const double2 (&v)[E], double s, __amdgpu_buffer_rsrc_t rs, int off, bool local) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) ring_store16(make_double2(v[e].x * s, v[e].y * s), rs, off + GS * e, local);
+}
+// mailbox slot -> LDS panel of nc columns by ng groups of GS lanes (this lane: group g, lane sub), every load sc1, all loads
+// of a lane in flight together: two columns per group where the planner can give a group two (w <= 32 against 16 groups of a
+// half up to 144 rows, w <= 8 against 4 waves of a half in the 64-lane form), one where it cannot (w <= 16 from 145 rows on) --
+// the loops only say that nothing is assumed.  The descriptor's range check returns zeros for a column that is not there.
+// norm[c] <- squared norm of column c, scale[c] <- 1 (bottom panels).
+template <int GS, int E>
+__device__ __forceinline__ void ring_recv_cols(double2* dst, const double2* slot, int nc, int g, int ng, int sub, double* norm,
+                                               double* scale) {
+    constexpr int mp = GS * E;
+    constexpr bool PAIRS = GS == 64 || E <= 9;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)slot, 0, nc * mp * 16, 0x00020000);
+    auto put = [&](int c, const ring_u4 (&u)[E]) {
+        if (c < nc) {
+            double2* col = dst + c * mp + sub;
+            double t = 0.0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                double2 v;
+                __builtin_memcpy(&v, &u[e], 16);
+                t = fma(v.x, v.x, fma(v.y, v.y, t));
+                col[GS * e] = v;
+            }
+            t = group_sum<GS>(t);
+            if (sub == 0) {
+                norm[c] = t;
+                if (scale) scale[c] = 1.0;
+            }
+        }
+    };
+    for (int c0 = g; c0 < nc; c0 += (PAIRS ? 2 : 1) * ng) {
+        ring_u4 u0[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) u0[e] = __builtin_amdgcn_raw_buffer_load_b128(rs, (c0 * mp + sub + GS * e) * 16, 0, 16);
+        if constexpr (PAIRS) {
+            const int c1 = c0 + ng;
+            ring_u4 u1[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) u1[e] = __builtin_amdgcn_raw_buffer_load_b128(rs, (c1 * mp + sub + GS * e) * 16, 0, 16);
+            put(c0, u0);
+            put(c1, u1);
+        } else put(c0, u0);
+    }
+}
+// where the register send of a round goes (ring_cross, SEND)
+struct RingOut {
+    __amdgpu_buffer_rsrc_t slot_t, slot_b;      // the neighbours' slots for this workgroup's top / bottom panel
+    bool send_t;                                // the top panel leaves (every workgroup but the first and the last)
+    bool keep_t;                                // the top panel is needed in this workgroup's LDS afterwards (first: it stays; last: it becomes the bottom)
+    bool local;
+};
+
 // Rotation of a column pair held in registers; returns the squared cosine seen.  With g = a^H b, h = |b|^2 - |a|^2:
 //   q = sign(h) 2 / (|h| + sqrt(h^2 + 4 |g|^2)) = tan / |g|,  c = 1 / sqrt(1 + q^2 |g|^2),
 //   [a' b'] = [a b] [[c, c q g], [-c q conj(g), c]]
@@ -2045,9 +2120,14 @@ struct RingStamps {
 //   a_st' = a_st - (q sb^2 conj(g_st)) b_st,   b_st' = b_st + (q sa^2 g_st) a_st,   sa' = c sa,   sb' = c sb
 // -- 8 real multiply-adds per element pair instead of 12 (the factor c moves into the two scales).  Scales start at 1 in
 // every round and are applied when the round ends (at most w factors c >= 1/sqrt 2 accumulate: no range issue).
-template <int GS, int E>
+// OUT = true (the round's last step when the columns leave from registers): b' goes, times its final scale, to column offset
+// out_off of the mailbox slot out_rs instead of to b_out, and `sent` is set; a pair that is not rotated leaves `sent` alone
+// and the caller sends b as it stands.  The same multiply-adds on the same operands.
+template <int GS, int E, bool OUT = false>
 __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const double2 (&b)[E], double2* b_out, double& aa, double& bb,
-                                                     double& sa, double& sb, double tol2, double zero2, RingStamps& st) {
+                                                     double& sa, double& sb, double tol2, double zero2, RingStamps& st,
+                                                     __amdgpu_buffer_rsrc_t out_rs = __amdgpu_buffer_rsrc_t(), int out_off = 0,
+                                                     bool out_local = false, bool* sent = nullptr) {
     // conj(a_st) * b_st in FOUR independent chains (even / odd elements x re / im): a dependent f64 multiply-add cannot issue
     // back to back, and with one busy wave per SIMD nothing else fills the slots
     double gr = 0.0, gi = 0.0, gr1 = 0.0, gi1 = 0.0;
@@ -2090,18 +2170,35 @@ __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const doub
     // covers the drain of the LDS writes that the barrier after the step waits for.  Interleaved per element, the last
     // writes left the VALU with nothing to do; the arithmetic is the same.  Cross rotations per sweep: 202 x 202 189 -> 180 us,
     // 400 x 400 486 -> 427 us (profiles/r04_ring_qr_phase_times.txt).
+    if constexpr (OUT) {
+        *sent = true;
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-        double2 nb;
-        nb.x = fma(-nui, a[e].y, fma(nur, a[e].x, b[e].x));
-        nb.y = fma(nui, a[e].x, fma(nur, a[e].y, b[e].y));
-        b_out[GS * e] = nb;
-    }
+        for (int e = 0; e < E; ++e) {
+            double2 nb;
+            nb.x = fma(-nui, a[e].y, fma(nur, a[e].x, b[e].x));
+            nb.y = fma(nui, a[e].x, fma(nur, a[e].y, b[e].y));
+            ring_store16(make_double2(nb.x * sb, nb.y * sb), out_rs, out_off + GS * e, out_local);
+        }
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-        double x = fma(-mur, b[e].x, a[e].x), y = fma(-mur, b[e].y, a[e].y);
-        a[e].x = fma(mui, b[e].y, x);
-        a[e].y = fma(-mui, b[e].x, y);
+        for (int e = 0; e < E; ++e) {
+            double x = fma(-mur, b[e].x, a[e].x), y = fma(-mur, b[e].y, a[e].y);
+            a[e].x = fma(mui, b[e].y, x);
+            a[e].y = fma(-mui, b[e].x, y);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            double2 nb;
+            nb.x = fma(-nui, a[e].y, fma(nur, a[e].x, b[e].x));
+            nb.y = fma(nui, a[e].x, fma(nur, a[e].y, b[e].y));
+            b_out[GS * e] = nb;
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            double x = fma(-mur, b[e].x, a[e].x), y = fma(-mur, b[e].y, a[e].y);
+            a[e].x = fma(mui, b[e].y, x);
+            a[e].y = fma(-mui, b[e].x, y);
+        }
     }
     RING_ST(st, 4);
     return ratio2;
@@ -2120,10 +2217,20 @@ __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const doub
 //     barrier is ~15 % of a step, the phase-2 read waits for the phase-1 writes, odd w wastes a phase per round) and one sweep
 //     more on some blocks of the headline: kept behind the switch.
 // split (diagnostic build): per-phase shader-clock sums of group 0 over the steps in which all its meetings rotated.
-template <int GS, int E, bool TWO>
+//   have_t / have_b: the panel came in through ring_recv_cols, which left the squared norms of its columns in tnorm[] /
+//     bnorm[] (and bscale[] = 1): nothing to recompute.
+//   SEND = true (TWO = false, nt > 0, nb > 0; the direct exchange): the round's LAST step hands the panels over from registers.
+//     In that step group g < wm holds B column j = (g + wm - 1) mod wm -- every B column exactly once: rotated in registers if
+//     g owns a T column, read from LDS as it stands if not (ragged panels) -- and stores it, times its scale, to the slot
+//     out.slot_b; group g < nt stores its T column to out.slot_t (send_t) and / or writes it to LDS (keep_t).  The bottom
+//     panel always leaves, so it is not written back to LDS, and there is no barrier here: the caller's drain + barrier
+//     before the flag is the next one.
+template <int GS, int E, bool TWO, bool SEND>
 __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int nb, int tid, double tol2, double zero2, double* bnorm,
-                                             double* bscale, long long* split) {
+                                             double* bscale, const double* tnorm, bool have_t, bool have_b, const RingOut& out,
+                                             long long* split) {
     static_assert(!TWO || GS == 16, "two partners per step need both rows of a pair in one wave");
+    static_assert(!(TWO && SEND), "the two-partner step keeps the staged send");
     constexpr int mp = GS * E;
     const int grp = tid / GS, sub = tid % GS;
     const int wm = nt > nb ? nt : nb;
@@ -2135,12 +2242,15 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
     if (own) {
 #pragma unroll
         for (int e = 0; e < E; ++e) a[e] = T[grp * mp + sub + GS * e];
-        double t = 0.0;
+        if (have_t) aa = tnorm[grp];
+        else {
+            double t = 0.0;
 #pragma unroll
-        for (int e = 0; e < E; ++e) t = fma(a[e].x, a[e].x, fma(a[e].y, a[e].y, t));
-        aa = group_sum<GS>(t);
+            for (int e = 0; e < E; ++e) t = fma(a[e].x, a[e].x, fma(a[e].y, a[e].y, t));
+            aa = group_sum<GS>(t);
+        }
     }
-    if (grp < nb) {            // exact squared norm of B column grp; its scale starts at 1
+    if (!have_b && grp < nb) {            // exact squared norm of B column grp; its scale starts at 1
         const double2* bc = B + grp * mp + sub;
         double sb = 0.0;
 #pragma unroll
@@ -2154,12 +2264,12 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
             bscale[grp] = 1.0;
         }
     }
-    __syncthreads();
+    if (!have_b) __syncthreads();      // (uniform; a received panel's norms were written before the barrier that ended the receive)
     constexpr int phases = TWO ? 2 : 1;
     const int hp = TWO ? (wm + 1) >> 1 : wm;                   // steps per round
     const int row = TWO ? (grp & 1) : 0, pr = TWO ? (grp >> 1) : grp;
     (void)split;
-    for (int s = 0; s < hp; ++s) {
+    for (int s = 0; s < (SEND ? hp - 1 : hp); ++s) {
         int jp = pr + s;
         jp = jp >= hp ? jp - hp : jp;                           // (pr < hp for every group that owns a T column)
 #ifdef HTN_RING_STEP_PROF
@@ -2211,6 +2321,33 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
             split[6] += phases;
         }
 #endif
+    }
+    if constexpr (SEND) {      // the last step: the columns leave from registers
+        int jp = pr + hp - 1;
+        jp = jp >= hp ? jp - hp : jp;
+        RingStamps st;
+        if (grp < hp && jp < nb) {
+            double2 b[E];
+            const double2* bc = B + jp * mp + sub;
+#pragma unroll
+            for (int e = 0; e < E; ++e) b[e] = bc[GS * e];
+            double bb = bnorm[jp], sb = bscale[jp];
+            bool sent = false;
+            if (own) {
+                const double rr = ring_rotate_scaled<GS, E, true>(a, b, nullptr, aa, bb, sa, sb, tol2, zero2, st, out.slot_b,
+                                                                  jp * mp + sub, out.local, &sent);
+                ratio = rr > ratio ? rr : ratio;
+            }
+            if (!sent) ring_send_col<GS, E>(b, sb, out.slot_b, jp * mp + sub, out.local);
+        }
+        if (own) {
+            if (out.send_t) ring_send_col<GS, E>(a, sa, out.slot_t, grp * mp + sub, out.local);
+            if (out.keep_t) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) T[grp * mp + sub + GS * e] = make_double2(a[e].x * sa, a[e].y * sa);
+            }
+        }
+        return ratio;
     }
     if (own) {                 // the scales come out with the columns: T from registers, B in place
 #pragma unroll
@@ -2293,6 +2430,7 @@ struct RingArgs {
     int xcc_off;                 // 32-bit words: one per workgroup, XCD id + 1 once the workgroup has started
     int max_sweeps;
     int two_partner;             // 1: two partner columns per cross step (HTN_RING_TWO_PARTNER=1, 16-lane form only)
+    int staged_send;             // 1: the staged panel exchange (HTN_RING_STAGED_SEND=1: ring_send / ring_recv)
     double tol;
     int* info;
     int* sweeps_out;             // host-mapped, [nl]: outer sweeps of each block (0 = failed)
@@ -2300,7 +2438,7 @@ struct RingArgs {
 
 template <int GS, int E>
 __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, const htn_svd_block D, double2* lds, int* s_top, int* s_bot,
-                         unsigned long long* s_rbits, int* s_ok, double* s_bnorm, int* s_local) {
+                         unsigned long long* s_rbits, int* s_ok, double* s_bnorm, int* s_local, unsigned* s_arr) {
     constexpr int mp = GS * E;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = it.P, k = it.k, w = it.w, n = it.n, m = D.m;
@@ -2322,6 +2460,7 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     }
     if (tid == 0) {
         *s_ok = 1;
+        s_arr[0] = s_arr[1] = 0u;
         // Which XCD is this?  The host places a block's workgroups at grid positions that the dispatcher has been SEEN to
         // deal to one XCD (position mod 8); nothing promises that, so every workgroup publishes the XCD id it reads from
         // the hardware register and the block takes the cheaper hand-off (plain stores kept in the shared L2) only if ALL
@@ -2362,7 +2501,9 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     __syncthreads();
 #ifdef HTN_RING_PROF
     // cross | send+drain | flags+wait | recv | intra | conv | total | sweeps,P | split of the cross steps (shader clock, see
-    // ring_cross): LDS read, dot + sums, angle, update + write, barrier, steps, meetings | shader clock over the run
+    // ring_cross): LDS read, dot + sums, angle, update + write, barrier, steps, meetings | shader clock over the run.
+    // Direct exchange: the mailbox stores are part of "cross" (its last step, which the step split does not count), "send+drain"
+    // is the drain + barrier, "flags+wait" lane 0's flags and the wait of its half, "recv" that half's loads + the common barrier
     long long prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const long long prof_t0 = wall_clock64();
     long long prof_c0;
@@ -2375,6 +2516,9 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     int sweeps = 0;
     bool done = n < 2, ok = *s_ok != 0;
     const int rounds = 2 * P - 1;
+    const bool direct = A.staged_send == 0;                     // the direct exchange (see ring_send_col)
+    double* const s_bscale = s_bnorm + RING_THREADS / 16;
+    double* const s_tnorm = s_bnorm + 2 * (RING_THREADS / 16);
     while (!done && ok && sweeps < A.max_sweeps) {
         double ratio = 0.0;
         for (int r = 0; r < rounds && ok; ++r) {
@@ -2382,63 +2526,108 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
             const int par = (int)(epoch & 1u);
             const int nt = ncols(s_top[k]), nb = ncols(s_bot[k]);
             RING_T(p0);
-            double rr;
-            if constexpr (GS == 16) {
-                if (A.two_partner) rr = ring_cross<GS, E, true>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16, split);
-                else rr = ring_cross<GS, E, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16, split);
-            } else {           // 64 lanes per column: the two rows of a pair would be two waves
-                rr = ring_cross<GS, E, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bnorm + RING_THREADS / 16, split);
-            }
+            double2* box = A.mbox + it.mbox;                    // slot of workgroup kd, role, parity: ((kd * 2 + role) * 2 + par)
+            // where this workgroup's panels go: top -> top of k + 1 (the first one's stays, the last one's becomes its bottom),
+            // bottom -> bottom of k - 1 (the first one's -> top of 1)
+            double2* const to_t = box + (int64_t)(((k + 1) * 2 + 0) * 2 + par) * slot_elems;
+            double2* const to_b = k == 0 ? box + (int64_t)((1 * 2 + 0) * 2 + par) * slot_elems
+                                         : box + (int64_t)(((k - 1) * 2 + 1) * 2 + par) * slot_elems;
+            const bool send_t = k > 0 && k < P - 1;
+            // a panel that came in through the direct receive brought its norms (not the first round of a sweep: the pairs
+            // inside the panels have been rotated since)
+            const bool have_t = direct && r > 0 && k > 0, have_b = direct && r > 0 && k < P - 1;
+            const bool reg_send = direct && !(GS == 16 && A.two_partner) && P > 1 && nt > 0 && nb > 0;
+            RingOut out;
+            out.slot_t = __builtin_amdgcn_make_buffer_rsrc((void*)to_t, 0, (reg_send && send_t) ? nt * mp * 16 : 0, 0x00020000);
+            out.slot_b = __builtin_amdgcn_make_buffer_rsrc((void*)to_b, 0, reg_send ? nb * mp * 16 : 0, 0x00020000);
+            out.send_t = send_t, out.keep_t = !send_t, out.local = local;
+            double rr = 0.0;
+            if (reg_send) rr = ring_cross<GS, E, false, true>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split);
+            else if (GS == 16 && A.two_partner) {
+                if constexpr (GS == 16)        // (64 lanes per column: the two rows of a pair would be two waves)
+                    rr = ring_cross<GS, E, true, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split);
+            } else rr = ring_cross<GS, E, false, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split);
             ratio = rr > ratio ? rr : ratio;
             RING_T(p1);
             RING_ACC(0, p0, p1);
             if (P < 2) continue;
-            // ---- panels move one position: send, drain, raise the flags ----
-            double2* box = A.mbox + it.mbox;                    // slot of workgroup kd, role, parity: ((kd * 2 + role) * 2 + par)
-            if (k == 0) ring_send(bufB, box + (int64_t)((1 * 2 + 0) * 2 + par) * slot_elems, nb * mp, tid, local);            // bottom -> top of 1
-            else {
-                if (k < P - 1) ring_send(bufT, box + (int64_t)(((k + 1) * 2 + 0) * 2 + par) * slot_elems, nt * mp, tid, local);   // top -> top of k + 1
-                ring_send(bufB, box + (int64_t)(((k - 1) * 2 + 1) * 2 + par) * slot_elems, nb * mp, tid, local);                  // bottom -> bottom of k - 1
+            // ---- panels move one position: send (unless the last cross step has done it), drain, raise the flags ----
+            if (!reg_send) {
+                if (send_t) ring_send(bufT, to_t, nt * mp, tid, local);
+                ring_send(bufB, to_b, nb * mp, tid, local);
             }
+            // the panels that come in (the ids follow the same permutation in every workgroup of the block; lane 0 applies it
+            // after the barrier)
+            const int in_top = k == 0 ? s_top[0] : (k == 1 ? s_bot[0] : s_top[k - 1]);
+            const int in_bot = k < P - 1 ? s_bot[k + 1] : s_top[P - 1];
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             RING_T(p2);
-            RING_ACC(1, p1, p2);
+            RING_ACC(1, p1, p2);          // (direct exchange: drain + barrier only, the stores are part of the cross phase)
+            // the direction a wave receives: 0 top, 1 bottom; a workgroup at an end of the ring has one direction for all waves
+            const int half = k == 0 ? 1 : (k == P - 1 ? 0 : wave >> 2);
+            const bool both = k > 0 && k < P - 1;
             if (tid == 0) {
                 if (k == 0) ring_flag(flags + (it.g0 + 1) * 2 + 0, epoch, local);
                 else {
                     if (k < P - 1) ring_flag(flags + (it.g0 + k + 1) * 2 + 0, epoch, local);
                     ring_flag(flags + (it.g0 + k - 1) * 2 + 1, epoch, local);
                 }
-                // the panel ids follow the same permutation in every workgroup of the block
                 const int t_last = s_top[P - 1], b0 = s_bot[0];
                 for (int q = P - 1; q >= 2; --q) s_top[q] = s_top[q - 1];
                 s_top[1] = b0;
                 for (int q = 0; q + 1 < P; ++q) s_bot[q] = s_bot[q + 1];
                 s_bot[P - 1] = t_last;
-                // ---- wait for what comes in ----
-                bool good = true;
-                if (k > 0) good = ring_wait_ge(flags + (it.g0 + k) * 2 + 0, epoch, fail);
-                if (good && k < P - 1) good = ring_wait_ge(flags + (it.g0 + k) * 2 + 1, epoch, fail);
-                if (!good) *s_ok = 0;
+                if (!direct) {
+                    // ---- wait for what comes in ----
+                    bool good = true;
+                    if (k > 0) good = ring_wait_ge(flags + (it.g0 + k) * 2 + 0, epoch, fail);
+                    if (good && k < P - 1) good = ring_wait_ge(flags + (it.g0 + k) * 2 + 1, epoch, fail);
+                    if (!good) *s_ok = 0;
+                }
             }
             if (k == P - 1) {           // the last workgroup's top panel becomes its bottom panel: swap the roles of the buffers
                 double2* t = bufT;
                 bufT = bufB;
                 bufB = t;
             }
-            __syncthreads();
-            RING_T(p3);
-            RING_ACC(2, p2, p3);
-            ok = *s_ok != 0;
-            if (ok) {
-                const double2* mine = box + (int64_t)(k * 4) * slot_elems;
-                if (k > 0) ring_recv(bufT, mine + (int64_t)(0 * 2 + par) * slot_elems, ncols(s_top[k]) * mp, tid);
-                if (k < P - 1) ring_recv(bufB, mine + (int64_t)(1 * 2 + par) * slot_elems, ncols(s_bot[k]) * mp, tid);
+            if (!direct) {
+                __syncthreads();
+                RING_T(p3);
+                RING_ACC(2, p2, p3);
+                ok = *s_ok != 0;
+                if (ok) {
+                    const double2* mine = box + (int64_t)(k * 4) * slot_elems;
+                    if (k > 0) ring_recv(bufT, mine + (int64_t)(0 * 2 + par) * slot_elems, ncols(s_top[k]) * mp, tid);
+                    if (k < P - 1) ring_recv(bufB, mine + (int64_t)(1 * 2 + par) * slot_elems, ncols(s_bot[k]) * mp, tid);
+                }
+                __syncthreads();
+                RING_T(p4);
+                RING_ACC(3, p3, p4);
+            } else {
+                // ---- each direction on its own: one lane polls the flag (bounded, as every poll), tells its half through LDS
+                // (epoch, or all ones: failed), the half loads; both halves meet at the barrier before the next round ----
+                if (tid == (both ? half * (RING_THREADS / 2) : 0)) {
+                    const bool good = ring_wait_ge(flags + (it.g0 + k) * 2 + half, epoch, fail);
+                    if (!good) *s_ok = 0;
+                    __hip_atomic_store(s_arr + half, good ? epoch : ~0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                unsigned seen;
+                while ((seen = __hip_atomic_load(s_arr + half, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < epoch)
+                    __builtin_amdgcn_s_sleep(1);
+                RING_T(p3);
+                RING_ACC(2, p2, p3);      // (lane 0: flags + the wait of ITS half)
+                if (seen != ~0u) {
+                    const double2* mine = box + (int64_t)(k * 4 + half * 2 + par) * slot_elems;
+                    const int ngt = RING_THREADS / GS, ng = both ? ngt / 2 : ngt, grp = tid / GS;
+                    ring_recv_cols<GS, E>(half ? bufB : bufT, mine, ncols(half ? in_bot : in_top), both ? grp % ng : grp, ng, tid % GS,
+                                          half ? s_bnorm : s_tnorm, half ? s_bscale : nullptr);
+                }
+                __syncthreads();
+                RING_T(p4);
+                RING_ACC(3, p3, p4);      // (lane 0: the loads of its half + the wait for the other half)
+                ok = *s_ok != 0;
             }
-            __syncthreads();
-            RING_T(p4);
-            RING_ACC(3, p3, p4);
         }
         if (!ok) break;
         RING_T(p5);
@@ -2523,25 +2712,26 @@ __global__ __launch_bounds__(RING_THREADS) void k_jacobi_ring(RingArgs A) {
     __shared__ int s_top[RING_MAX_P], s_bot[RING_MAX_P];
     __shared__ unsigned long long s_rbits;
     __shared__ int s_ok, s_local;
-    __shared__ double s_bnorm[2 * (RING_THREADS / 16)];      // tracked squared norms | scales of the bottom panel's columns
+    __shared__ double s_bnorm[3 * (RING_THREADS / 16)];      // tracked squared norms | scales of the bottom panel's columns | norms of a received top panel
+    __shared__ unsigned s_arr[2];                            // direct receive: the epoch whose top / bottom panel has arrived
     const RingItem it = A.items[blockIdx.x];
     if (it.P <= 0) return;           // (a gap of the XCD-aware placement: see plan_ring)
     const htn_svd_block D = A.desc[A.large_ids[it.li]];
     const int m = D.m;
     const int gs = ring_gs(m), E = ring_e(m);
 #define RING_CASE(GSV, EV) \
-    case EV: ring_run<GSV, EV>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local); break;
+    case EV: ring_run<GSV, EV>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local, s_arr); break;
     if (gs == 16) {                  // m <= 256
         switch (E) {
             RING_CASE(16, 1) RING_CASE(16, 2) RING_CASE(16, 3) RING_CASE(16, 4) RING_CASE(16, 5) RING_CASE(16, 6) RING_CASE(16, 7)
             RING_CASE(16, 8) RING_CASE(16, 9) RING_CASE(16, 10) RING_CASE(16, 11) RING_CASE(16, 12) RING_CASE(16, 13)
             RING_CASE(16, 14) RING_CASE(16, 15)
-            default: ring_run<16, 16>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local);
+            default: ring_run<16, 16>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local, s_arr);
         }
     } else {                         // 256 < m <= 512: E = 5 .. 8
         switch (E) {
             RING_CASE(64, 5) RING_CASE(64, 6) RING_CASE(64, 7)
-            default: ring_run<64, 8>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local);
+            default: ring_run<64, 8>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local, s_arr);
         }
     }
 #undef RING_CASE
@@ -2900,7 +3090,7 @@ static int launch_qr_large(const JacCall& c, JacScratch& js, const JacCoreBufs& 
 // Ring path: all sweeps of the large blocks in one launch per batch, then the join with the small blocks and the host's
 // look at the sweep counts
 static int run_ring(const JacCall& c, JacScratch& js, const JacCoreBufs& B, const RingPlan& plan, int n_xcd, bool two_partner,
-                    int32_t* sweeps_used) {
+                    bool staged_send, int32_t* sweeps_used) {
     const int nl = c.nl(), n_wg = plan.wgs, n_items = (int)plan.items.size();
     // sync block (32-bit words): [flags: 2 per workgroup | arrivals: nl x max_sweeps | failure word | XCD ids: 1 per
     // workgroup | pad] then the 64-bit maxima, nl x max_sweeps; zeroed as ONE block that starts its allocation and is a
@@ -2921,6 +3111,7 @@ static int run_ring(const JacCall& c, JacScratch& js, const JacCoreBufs& B, cons
     ra.arrive_off = arrive_off, ra.fail_off = fail_off, ra.conv_off = conv_off, ra.max_sweeps = c.max_sweeps, ra.tol = c.tol;
     ra.xcc_off = xcc_off;
     ra.two_partner = two_partner ? 1 : 0;
+    ra.staged_send = staged_send ? 1 : 0;
     ra.info = c.info_dev, ra.sweeps_out = B.d_ring_sw;
     for (auto& bt : plan.batches) {
         ra.items = (const RingItem*)js.ring_items.p + bt.first;
@@ -3022,6 +3213,9 @@ static int jacobi_svd_core(void* G, void* Vj, double* S, const htn_svd_block* de
     // reads at run time, hands panels over through that L2.  Speed only: a block whose workgroups find themselves on
     // different XCDs uses the placement-independent hand-off.  HTN_RING_NO_XCD=1: dense placement, as before.
     static const bool no_xcd = htn_env_flag("HTN_RING_NO_XCD");
+    // HTN_RING_STAGED_SEND=1: the panel exchange of the ring kernel staged through LDS (ring_send / ring_recv) instead of the
+    // direct one (ring_send_col / ring_recv_cols); same bits, the reference for tests and phase times
+    static const bool ring_staged = htn_env_flag("HTN_RING_STAGED_SEND");
     // HTN_RING_TWO_PARTNER=1: cross steps with two partner columns each (ring_cross; measured no faster);
     // read at every call, so one process can run both forms
     const bool ring_two_partner = htn_env_flag("HTN_RING_TWO_PARTNER");
@@ -3052,7 +3246,7 @@ static int jacobi_svd_core(void* G, void* Vj, double* S, const htn_svd_block* de
             if (upload_tournament(T, B.h_items, B.d_items, c.st)) return 1;
         }
     }
-    if (use_ring) return run_ring(c, js, B, plan, n_xcd, ring_two_partner, sweeps_used);
+    if (use_ring) return run_ring(c, js, B, plan, n_xcd, ring_two_partner, ring_staged, sweeps_used);
     return run_pair_visits(c, js, B, T, opts && opts->sweeps_hint > 0 ? opts->sweeps_hint : 0, sweeps_used);
 }
 

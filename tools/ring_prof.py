@@ -1,5 +1,10 @@
 """diagnostic: per-phase time of k_jacobi_ring on one block (needs a library built with HTN_EXTRA_FLAGS=-DHTN_RING_PROF; with
--DHTN_RING_STEP_PROF as well it also splits a cross step into its phases, at the price of slower steps)"""
+-DHTN_RING_STEP_PROF as well it also splits a cross step into its phases, at the price of slower steps).
+
+With the direct panel exchange (the default) the columns are stored to the neighbour's mailbox inside the last cross step, so
+"cross" holds those stores, "send+drain" is the drain plus the barrier before the flag, "flags+wait" is lane 0 raising the flags
+and the wait of ITS half of the workgroup for its panel, and "recv" the loads of that half plus the wait for the other half at
+the common barrier.  HTN_RING_STAGED_SEND=1 in the environment gives the staged exchange with the phases as named."""
 import ctypes as C
 import sys
 import numpy as np
