@@ -330,10 +330,42 @@ struct DBuf {
     DBuf& operator=(const DBuf&) = delete;
 };
 typedef std::shared_ptr<DBuf> DBufP;
+// device buffer of host data (copy items, descriptors, column indices, scale factors, small matrices)
+template <class T>
+DBufP upload_vec(Backend* be, const std::vector<T>& v) {
+    auto b = std::make_shared<DBuf>(be, sizeof(T) * std::max<size_t>(v.size(), 1));
+    if (!b->p) return nullptr;
+    if (!v.empty() && be->upload(b->p, v.data(), sizeof(T) * v.size())) return nullptr;
+    return b;
+}
 struct DView {                     // complex128 window of a device buffer
     DBufP base;
     int64_t off = 0;
     cplx* ptr() const { return base ? (cplx*)base->p + off : nullptr; }
+};
+
+// plain rows x cols copy, op N: no gather, no scaling (callers set what differs)
+htn_copy_item copy_item(int64_t dst_off, int32_t ldd, int64_t src_off, int32_t lds, int32_t rows, int32_t cols) {
+    htn_copy_item it;
+    memset(&it, 0, sizeof(it));
+    it.dst_off = dst_off, it.src_off = src_off, it.idx_off = -1, it.scl_off = -1;
+    it.rows = rows, it.cols = cols, it.ldd = ldd, it.lds = lds, it.op = HTN_OP_N, it.scale_dim = -1;
+    return it;
+}
+
+// host wall time of the stages of one update; with `profile` every lap ends in a stream sync (GPU-inclusive times)
+struct StageClock {
+    Backend* be;
+    bool profile;
+    double t0, last;
+    double plan = 0.0, lanczos = 0.0, svd = -1.0, env = 0.0;      // svd < 0: what the other stages leave of the total
+    StageClock(Backend* b, bool p) : be(b), profile(p), t0(now()), last(t0) {}
+    double lap() {
+        if (profile) be->sync();
+        const double t = now(), d = t - last;
+        last = t;
+        return d;
+    }
 };
 
 struct DevTasks {
@@ -351,11 +383,14 @@ struct ApplyC {
     int64_t zsize = 0, flops = 0;
     int32_t ntiles = 0, nsegs = 0;
 };
-struct EnvC {
-    EnvLayoutP lay;
+template <class Lay>
+struct TwoStageC {                 // compiled two-stage contraction (EnvPlan / OvlPlan): stage 1 -> BUF_Z, stage 2 -> BUF_Y
+    std::shared_ptr<const Lay> lay;        // layout of the result (not set: the caller names it -- projector rows)
     DevTasks d1, d2;
     int64_t zsize = 0, flops = 0;
 };
+typedef TwoStageC<EnvLayout> EnvC;
+typedef TwoStageC<OvlLayout> OvlC;
 struct SvdC {
     SvdPlan sp;
     DBufP stage, desc;
@@ -377,11 +412,6 @@ struct Spectrum {
     std::vector<Sec> secs;
     std::vector<std::vector<double>> vals;
 };
-struct OvlC {                      // compiled overlap transfer / projection (plan_ovl_*)
-    OvlLayoutP lay;                // layout of the result (transfers)
-    DevTasks d1, d2;
-    int64_t zsize = 0;
-};
 struct RelayC {                    // copy items that re-lay a site tensor from one layout kind to another (or copy it)
     DBufP items;
     int n = 0;
@@ -396,6 +426,30 @@ struct OrthState {                 // one attached state phi: overlap environmen
     htn_mps* phi = nullptr;
     std::vector<OvlLayoutP> Llay, Rlay;
     std::vector<DView> Lbuf, Rbuf;
+};
+struct Solve {                     // the eigenproblem of one update (compiled apply, vector length) and what the solver returned
+    std::shared_ptr<ApplyC> ap;
+    int64_t n = 0;
+    double E = 0.0, res = 0.0, mv_ms = 0.0;
+    int nmv = 0;
+};
+struct BondWork {                  // what flows between the steps of one two-site update (htn_mps::update_bond)
+    ThetaLayoutP tl;
+    Solve sol;
+    // device buffers: all live until the update returns and go back to the pool in reverse order of declaration
+    DView V, z, Qb;                // Krylov basis (row 0: theta, then the optimised tensor); Z stage of the apply; projector rows
+    std::shared_ptr<SvdC> sc;
+    DView G, Vj;
+    DBufP S, idx;                  // s_elems singular values | per-block sweep counts (int32); kept columns, block after block
+    size_t s_elems = 0;
+    std::vector<double> s_host;    // host copy of S
+    int jac_sweeps = 0;
+    std::vector<int> lens, qd, counts;     // per block: values, quantum dimension, kept values
+    std::vector<std::vector<int>> order;   // per block: its columns by descending value
+    std::vector<double> vals;              // all values, block after block, each block descending
+    double nrm = 0.0, tw = 0.0;
+    BondP mid;
+    double tA = 0.0, tB = 0.0, tC = 0.0, tD = 0.0;      // HTN_DEBUG_HOST_TIMERS: after the SVD call, download, truncation, finalise plan
 };
 
 }  // namespace
@@ -503,74 +557,73 @@ struct htn_mps {
         return be->grouped_gemm(table, d.tiles, d.ntiles, d.segs);
     }
 
-    int left_env(int i);
-    int right_env(int i);
+    // compiled two-stage plan: upload t1 and t2, record zsize (and the flops)
+    template <class C, class P>
+    std::shared_ptr<C> compile2(std::shared_ptr<C> e, const P& p) {
+        if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
+        e->zsize = p.zsize;
+        e->flops = p.t1.flops + p.t2.flops;
+        return e;
+    }
+    int env_step(char side, int i);
+    int left_env(int i) { return env_step('L', i); }
+    int right_env(int i) { return env_step('R', i); }
     // overlap transfers with `ket` as the ket state (this = bra): in -> out across site i
-    int ovl_left(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);
-    int ovl_right(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);
+    int ovl_step(char side, const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);
     int ovl_boundary(const htn_mps* ket, int b, OvlLayoutP* outl, DView* out);
     int ovl_project(const OrthState& o, int i, const ThetaLayout& tl, cplx* dst);
     int orth_attach(htn_mps* const* others, int n);
     void orth_detach();
+    // H_eff applies (two-site: make_apply, one-site: make_apply1)
+    std::shared_ptr<ApplyC> compile_apply(ApplyPlan& p, bool deal_y);
     std::shared_ptr<ApplyC> make_apply(int i, const ThetaLayout& tl);
+    std::shared_ptr<ApplyC> make_apply1(int i, const SiteLayout& lay);
+    int apply_stages(const ApplyC& ap, const DView& L, const DView& R, const DView& z, htn_gemm_launch* stages);
+    int apply_once(const ApplyC& ap, const DView& L, const DView& R, int64_t n, const void* x_host, void* y_host, bool exchange);
     int theta_into(int i, const ThetaLayout& tl, cplx* dst);
+    // two-site update: update_bond runs these once each, in this order
+    int bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w);
+    std::shared_ptr<SvdC> make_svd(int i, const ThetaLayout& tl, bool right);
+    int bond_svd(int i, bool right, const htn_sweep_opts& o, BondWork& w);
+    int bond_truncate(int i, const htn_sweep_opts& o, BondWork& w);
+    int bond_finalise(int i, bool right, BondWork& w);
+    int bond_advance(int i, bool right);
+    void bond_spectrum(int i, const BondWork& w);
+    void fill_stats(htn_bond_stats* st, int bond, int direction, const Solve& sol, int64_t env_elems, int jacobi_sweeps,
+                    int64_t svd_flops, double trunc_weight, const StageClock& clk);
     int update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
     int sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
     // one-site DMRG (htn_site_update / htn_dmrg1_sweep)
-    std::shared_ptr<ApplyC> make_apply1(int i, const SiteLayout& lay);
-    int heff1_stages(int i, const ApplyC& ap, const DView& z, htn_gemm_launch* stages);
     int relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst);
     int update_site(int i, int direction, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
     int sweep1(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
 };
 
-// GL on bond i+1 from GL on bond i and the left-layout tensor of site i
-int htn_mps::left_env(int i) {
+// One step of the H environment across site i.  side 'L': GL on bond i+1 from GL on bond i and the left-layout tensor of
+// site i; side 'R': GR on bond i from GR on bond i+1 and the right-layout tensor of site i
+int htn_mps::env_step(char side, int i) {
+    const bool left = side == 'L';
     const SiteLayout& lay = *site_lay[i];
-    if (lay.kind != 'L') return set_error("left_env: site %d is not in left layout", i);
+    if (lay.kind != side)
+        return left ? set_error("left_env: site %d is not in left layout", i) : set_error("right_env: site %d is not in right layout", i);
     const MpoSite& W = mpo->sites[i];
-    auto c = cached<EnvC>(ikey("lenv", i) + bonds[i]->key + "|" + bonds[i + 1]->key, [&]() -> std::shared_ptr<EnvC> {
+    const int from = left ? i : i + 1, to = left ? i + 1 : i;
+    std::vector<EnvLayoutP>& elay = left ? Llay : Rlay;
+    std::vector<DView>& ebuf = left ? Lbuf : Rbuf;
+    auto c = cached<EnvC>(ikey(left ? "lenv" : "renv", i) + bonds[i]->key + "|" + bonds[i + 1]->key, [&]() -> std::shared_ptr<EnvC> {
         auto e = std::make_shared<EnvC>();
-        e->lay = build_env_layout(mpo->sym, 'L', bonds[i + 1], W.right);
+        e->lay = build_env_layout(mpo->sym, side, bonds[to], left ? W.right : W.left);
         EnvPlan p;
-        plan_left_env(*mpo, *Llay[i], lay, W, *e->lay, p);
-        if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
-        e->zsize = p.zsize;
-        e->flops = p.t1.flops + p.t2.flops;
-        return e;
+        (left ? plan_left_env : plan_right_env)(*mpo, *elay[from], lay, W, *e->lay, p);
+        return compile2(e, p);
     });
     if (!c) return 1;
     DView z = zalloc(c->zsize, false), out = zalloc(c->lay->size, false);
-    if (!z.base || !out.base) return set_error("device allocation failed (left environment)");
-    if (gemm(c->d1, {{BUF_L, Lbuf[i].ptr()}, {BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (!z.base || !out.base) return set_error("device allocation failed (%s environment)", left ? "left" : "right");
+    if (gemm(c->d1, {{left ? BUF_L : BUF_R, ebuf[from].ptr()}, {BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
     if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, out.ptr()}})) return 1;
-    Llay[i + 1] = c->lay;
-    Lbuf[i + 1] = out;
-    return 0;
-}
-
-// GR on bond i from GR on bond i+1 and the right-layout tensor of site i
-int htn_mps::right_env(int i) {
-    const SiteLayout& lay = *site_lay[i];
-    if (lay.kind != 'R') return set_error("right_env: site %d is not in right layout", i);
-    const MpoSite& W = mpo->sites[i];
-    auto c = cached<EnvC>(ikey("renv", i) + bonds[i]->key + "|" + bonds[i + 1]->key, [&]() -> std::shared_ptr<EnvC> {
-        auto e = std::make_shared<EnvC>();
-        e->lay = build_env_layout(mpo->sym, 'R', bonds[i], W.left);
-        EnvPlan p;
-        plan_right_env(*mpo, *Rlay[i + 1], lay, W, *e->lay, p);
-        if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
-        e->zsize = p.zsize;
-        e->flops = p.t1.flops + p.t2.flops;
-        return e;
-    });
-    if (!c) return 1;
-    DView z = zalloc(c->zsize, false), out = zalloc(c->lay->size, false);
-    if (!z.base || !out.base) return set_error("device allocation failed (right environment)");
-    if (gemm(c->d1, {{BUF_R, Rbuf[i + 1].ptr()}, {BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
-    if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, out.ptr()}})) return 1;
-    Rlay[i] = c->lay;
-    Rbuf[i] = out;
+    elay[to] = c->lay;
+    ebuf[to] = out;
     return 0;
 }
 
@@ -586,46 +639,24 @@ int htn_mps::ovl_boundary(const htn_mps* ket, int b, OvlLayoutP* outl, DView* ou
     return 0;
 }
 
-int htn_mps::ovl_left(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out) {
+// side 'L': O_L[bra x ket] moves from bond i to bond i+1; side 'R': O_R[ket x bra] from bond i+1 to bond i (the output is
+// zero-filled: a transfer leaves sectors without a contribution unwritten)
+int htn_mps::ovl_step(char side, const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out) {
+    const bool left = side == 'L';
     const SiteLayout &lb = *site_lay[i], &lk = *ket->site_lay[i];
-    auto c = cached<OvlC>(std::string("ovlL") + lb.kind + lk.kind + bonds[i]->key + "|" + bonds[i + 1]->key + "|" + ket->bonds[i]->key + "|" +
-                              ket->bonds[i + 1]->key,
+    auto c = cached<OvlC>(std::string(left ? "ovlL" : "ovlR") + lb.kind + lk.kind + bonds[i]->key + "|" + bonds[i + 1]->key + "|" +
+                              ket->bonds[i]->key + "|" + ket->bonds[i + 1]->key,
                           [&]() -> std::shared_ptr<OvlC> {
                               auto e = std::make_shared<OvlC>();
-                              e->lay = build_ovl_layout(bonds[i + 1], ket->bonds[i + 1]);
+                              e->lay = left ? build_ovl_layout(bonds[i + 1], ket->bonds[i + 1]) : build_ovl_layout(ket->bonds[i], bonds[i]);
                               OvlPlan p;
-                              plan_ovl_left(*inl, lb, lk, *e->lay, p);
-                              if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
-                              e->zsize = p.zsize;
-                              return e;
+                              (left ? plan_ovl_left : plan_ovl_right)(*inl, lb, lk, *e->lay, p);
+                              return compile2(e, p);
                           });
     if (!c) return 1;
     DView z = zalloc(c->zsize, false), o = zalloc(c->lay->size, true);
     if (!z.base || !o.base) return set_error("device allocation failed (overlap environment)");
-    if (gemm(c->d1, {{BUF_L, in.ptr()}, {BUF_S2, ket->site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
-    if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
-    *outl = c->lay;
-    *out = o;
-    return 0;
-}
-
-int htn_mps::ovl_right(const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out) {
-    const SiteLayout &lb = *site_lay[i], &lk = *ket->site_lay[i];
-    auto c = cached<OvlC>(std::string("ovlR") + lb.kind + lk.kind + bonds[i]->key + "|" + bonds[i + 1]->key + "|" + ket->bonds[i]->key + "|" +
-                              ket->bonds[i + 1]->key,
-                          [&]() -> std::shared_ptr<OvlC> {
-                              auto e = std::make_shared<OvlC>();
-                              e->lay = build_ovl_layout(ket->bonds[i], bonds[i]);
-                              OvlPlan p;
-                              plan_ovl_right(*inl, lb, lk, *e->lay, p);
-                              if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
-                              e->zsize = p.zsize;
-                              return e;
-                          });
-    if (!c) return 1;
-    DView z = zalloc(c->zsize, false), o = zalloc(c->lay->size, true);
-    if (!z.base || !o.base) return set_error("device allocation failed (overlap environment)");
-    if (gemm(c->d1, {{BUF_R, in.ptr()}, {BUF_S2, ket->site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (gemm(c->d1, {{left ? BUF_L : BUF_R, in.ptr()}, {BUF_S2, ket->site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
     if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
     *outl = c->lay;
     *out = o;
@@ -639,12 +670,9 @@ int htn_mps::ovl_project(const OrthState& os, int i, const ThetaLayout& tl, cplx
     auto c = cached<OvlC>(std::string("ovlP") + k1.kind + k2.kind + bonds[i]->key + "|" + bonds[i + 2]->key + "|" + ket->bonds[i]->key + "|" +
                               ket->bonds[i + 1]->key + "|" + ket->bonds[i + 2]->key,
                           [&]() -> std::shared_ptr<OvlC> {
-                              auto e = std::make_shared<OvlC>();
                               OvlPlan p;
                               plan_ovl_project(*os.Llay[i], *os.Rlay[i + 2], k1, k2, tl, p);
-                              if (upload_tasks(p.t1, e->d1) || upload_tasks(p.t2, e->d2)) return nullptr;
-                              e->zsize = p.zsize;
-                              return e;
+                              return compile2(std::make_shared<OvlC>(), p);
                           });
     if (!c) return 1;
     DView z = zalloc(c->zsize, false);
@@ -674,9 +702,9 @@ int htn_mps::orth_attach(htn_mps* const* others, int n) {
         os.Rbuf.resize(L + 1);
         if (ovl_boundary(os.phi, 0, &os.Llay[0], &os.Lbuf[0]) || ovl_boundary(os.phi, L, &os.Rlay[L], &os.Rbuf[L])) return 1;
         for (int i = 0; i < L; ++i)
-            if (ovl_left(os.phi, i, os.Llay[i], os.Lbuf[i], &os.Llay[i + 1], &os.Lbuf[i + 1])) return 1;
+            if (ovl_step('L', os.phi, i, os.Llay[i], os.Lbuf[i], &os.Llay[i + 1], &os.Lbuf[i + 1])) return 1;
         for (int i = L - 1; i >= 0; --i)
-            if (ovl_right(os.phi, i, os.Rlay[i + 1], os.Rbuf[i + 1], &os.Rlay[i], &os.Rbuf[i])) return 1;
+            if (ovl_step('R', os.phi, i, os.Rlay[i + 1], os.Rbuf[i + 1], &os.Rlay[i], &os.Rbuf[i])) return 1;
     }
     if (be->sync()) return 1;
     for (int k = 0; k < n; ++k) ++others[k]->refs;
@@ -685,29 +713,64 @@ int htn_mps::orth_attach(htn_mps* const* others, int n) {
     return 0;
 }
 
-// compiled H_eff apply of bond (i, i+1); with a sharded context the Y-stage tiles are dealt round-robin over the ranks
-// (tiles are in LPT order, so dealing balances MACs; every rank keeps the full segment table and the full Z stage)
+// ---- H_eff applies -----------------------------------------------------------------------------------------------------
+// ApplyPlan -> ApplyC: counts for the statistics, then the Z and Y lists on the device.  deal_y (the two-site apply): with
+// more than one rank the Y-stage tiles are dealt round-robin over the ranks first (tiles are in LPT order, so dealing
+// balances MACs; every rank keeps the full segment table and the full Z stage; an empty deal keeps one tile)
+std::shared_ptr<ApplyC> htn_mps::compile_apply(ApplyPlan& p, bool deal_y) {
+    auto a = std::make_shared<ApplyC>();
+    a->has_z = p.has_z;
+    a->zsize = p.zsize;
+    a->flops = p.ty.flops + (p.has_z ? p.tz.flops : 0);
+    a->ntiles = p.ty.ntiles + (p.has_z ? p.tz.ntiles : 0);
+    a->nsegs = p.ty.nsegs + (p.has_z ? p.tz.nsegs : 0);
+    if (deal_y && ctx->world > 1) {
+        std::vector<htn_tile> sel;
+        for (int t = ctx->rank; t < p.ty.ntiles; t += ctx->world) sel.push_back(p.ty.tiles[t]);
+        p.ty.ntiles = (int32_t)sel.size();
+        if (sel.empty()) sel.push_back(p.ty.tiles[0]);
+        p.ty.tiles.swap(sel);
+    }
+    if (p.has_z && upload_tasks(p.tz, a->dz)) return nullptr;
+    if (upload_tasks(p.ty, a->dy)) return nullptr;
+    return a;
+}
+
+// compiled H_eff apply of bond (i, i+1)
 std::shared_ptr<ApplyC> htn_mps::make_apply(int i, const ThetaLayout& tl) {
     return cached<ApplyC>(ikey("apply", i) + bonds[i]->key + "|" + bonds[i + 2]->key, [&]() -> std::shared_ptr<ApplyC> {
         ApplyPlan p;
         plan_apply(*mpo, tl, *Llay[i], *Rlay[i + 2], mpo->sites[i], mpo->sites[i + 1], p);
-        auto a = std::make_shared<ApplyC>();
-        a->has_z = p.has_z;
-        a->zsize = p.zsize;
-        a->flops = p.ty.flops + (p.has_z ? p.tz.flops : 0);
-        a->ntiles = p.ty.ntiles + (p.has_z ? p.tz.ntiles : 0);
-        a->nsegs = p.ty.nsegs + (p.has_z ? p.tz.nsegs : 0);
-        if (ctx->world > 1) {
-            std::vector<htn_tile> sel;
-            for (int t = ctx->rank; t < p.ty.ntiles; t += ctx->world) sel.push_back(p.ty.tiles[t]);
-            p.ty.ntiles = (int32_t)sel.size();
-            if (sel.empty()) sel.push_back(p.ty.tiles[0]);
-            p.ty.tiles.swap(sel);
-        }
-        if (p.has_z && upload_tasks(p.tz, a->dz)) return nullptr;
-        if (upload_tasks(p.ty, a->dy)) return nullptr;
-        return a;
+        return compile_apply(p, true);
     });
+}
+// compiled one-site H_eff apply of site i in the layout `lay`
+std::shared_ptr<ApplyC> htn_mps::make_apply1(int i, const SiteLayout& lay) {
+    return cached<ApplyC>(ikey("apply1", i) + lay.kind + bonds[i]->key + "|" + bonds[i + 1]->key, [&]() -> std::shared_ptr<ApplyC> {
+        ApplyPlan p;
+        plan_apply1(*mpo, lay, *Llay[i], *Rlay[i + 1], mpo->sites[i], p);
+        return compile_apply(p, false);
+    });
+}
+
+// stage table of an apply between the environments L and R (the Z stage if the plan has one, then the Y stage), split-K
+// workspace ensured; the Lanczos driver fills in x and y.  -> number of stages, < 0 on error
+int htn_mps::apply_stages(const ApplyC& ap, const DView& L, const DView& R, const DView& z, htn_gemm_launch* stages) {
+    if (ensure_ws(std::max(ap.dy.ws_slots, ap.has_z ? ap.dz.ws_slots : 0))) return -1;
+    memset(stages, 0, 2 * sizeof(htn_gemm_launch));
+    stages[0].bufs[HTN_BUF_WS] = stages[1].bufs[HTN_BUF_WS] = ws.ptr();
+    int ns = 0;
+    if (ap.has_z) {
+        stages[ns].bufs[BUF_L] = L.ptr();
+        stages[ns].bufs[BUF_Z] = z.ptr();
+        stages[ns].tiles = ap.dz.tiles, stages[ns].segs = ap.dz.segs, stages[ns].n_tiles = ap.dz.ntiles;
+        ++ns;
+    }
+    stages[ns].bufs[BUF_L] = L.ptr();
+    stages[ns].bufs[BUF_R] = R.ptr();
+    stages[ns].bufs[BUF_Z] = z.ptr();
+    stages[ns].tiles = ap.dy.tiles, stages[ns].segs = ap.dy.segs, stages[ns].n_tiles = ap.dy.ntiles;
+    return ns + 1;
 }
 
 int htn_mps::theta_into(int i, const ThetaLayout& tl, cplx* dst) {
@@ -732,77 +795,87 @@ static int exchange_tramp(void* y, int64_t n, void* user) {
     return ctx->be->allreduce(y, n);
 }
 
-int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st) {
-    if (i < 0 || i + 1 >= L) return set_error("htn_bond_update: bond index %d out of range", i);
-    const double t0 = now();
-    const Sym& sym = mpo->sym;
-    BondP bl = bonds[i], br = bonds[i + 2];
-    ThetaLayoutP tlp = theta_layout(bl, br);
-    const ThetaLayout& tl = *tlp;
-    const int64_t n = tl.size;
-    const int kd = o.krylovdim > 0 ? o.krylovdim : 30;
+// y = H_eff x once, host to host (htn_heff1_apply / htn_heff2_apply): upload x, Z stage, Y stage, download y; `exchange`:
+// sum y over the ranks first (only the two-site entry shards its apply)
+int htn_mps::apply_once(const ApplyC& ap, const DView& L, const DView& R, int64_t n, const void* x_host, void* y_host, bool exchange) {
+    DView x = zalloc(n, false), y = zalloc(n, true), z = zalloc(ap.zsize, false);
+    if (!x.base || !y.base || !z.base) return set_error("device allocation failed");
+    if (be->upload(x.ptr(), x_host, sizeof(cplx) * n)) return 1;
+    if (ap.has_z && gemm(ap.dz, {{BUF_X, x.ptr()}, {BUF_L, L.ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (gemm(ap.dy, {{BUF_X, x.ptr()}, {BUF_Y, y.ptr()}, {BUF_L, L.ptr()}, {BUF_R, R.ptr()}, {BUF_Z, z.ptr()}})) return 1;
+    if (exchange && exchange_tramp(y.ptr(), n, ctx)) return set_error("htn_heff2_apply: exchange failed");
+    return be->download(y_host, y.ptr(), sizeof(cplx) * n);
+}
+
+void htn_mps::fill_stats(htn_bond_stats* st, int bond, int direction, const Solve& sol, int64_t env_elems, int jacobi_sweeps,
+                         int64_t svd_flops, double trunc_weight, const StageClock& clk) {
+    memset(st, 0, sizeof(*st));
+    st->bond = bond, st->direction = direction;
+    st->n_matvec = sol.nmv, st->jacobi_sweeps = jacobi_sweeps;
+    st->chi_full = (int32_t)bonds[bond]->dim_full(mpo->sym), st->multiplets = bonds[bond]->multiplets();
+    st->n_tiles = sol.ap->ntiles, st->n_segs = sol.ap->nsegs;
+    st->theta_size = sol.n;
+    st->apply_flops = sol.ap->flops, st->apply_bytes = 16 * (2 * sol.n + env_elems), st->svd_flops = svd_flops;
+    st->energy = sol.E, st->residual = sol.res, st->trunc_weight = trunc_weight;
+    st->t_plan = clk.plan, st->t_lanczos = clk.lanczos, st->t_env = clk.env;
+    st->t_total = now() - clk.t0;
+    st->t_svd = clk.svd >= 0.0 ? clk.svd : st->t_total - clk.plan - clk.lanczos - clk.env;
+    st->matvec_ms = sol.mv_ms > 0.0 ? sol.mv_ms : 0.0;      // (0: none of this solve's launches fell on the 1-in-8 timing sample)
+}
+
+// ---- two-site update, step by step ----------------------------------------------------------------
+// solve: theta -> V[0], the compiled apply, the projector rows of attached states (optimising updates), Lanczos
+int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w) {
+    w.tl = theta_layout(bonds[i], bonds[i + 2]);
+    const ThetaLayout& tl = *w.tl;
+    Solve& s = w.sol;
+    const int64_t n = s.n = tl.size;
+    const int kd = o.krylovdim;
     if (n <= 0) return set_error("htn_bond_update: empty two-site tensor on bond %d", i);
-    DView V = zalloc((int64_t)(kd + 2) * n, false);
-    if (!V.base) return set_error("device allocation of the Krylov basis failed (%lld elements)", (long long)((kd + 2) * n));
-    if (theta_into(i, tl, V.ptr())) return 1;                  // theta -> V[0] (the Lanczos driver normalises it)
-    auto ap = make_apply(i, tl);
-    if (!ap) return 1;
-    DView z = zalloc(ap->zsize, false);
-    if (ensure_ws(std::max(ap->dy.ws_slots, ap->has_z ? ap->dz.ws_slots : 0))) return 1;
+    w.V = zalloc((int64_t)(kd + 2) * n, false);
+    if (!w.V.base) return set_error("device allocation of the Krylov basis failed (%lld elements)", (long long)((kd + 2) * n));
+    if (theta_into(i, tl, w.V.ptr())) return 1;                // theta -> V[0] (the Lanczos driver normalises it)
+    s.ap = make_apply(i, tl);
+    if (!s.ap) return 1;
+    w.z = zalloc(s.ap->zsize, false);
     htn_gemm_launch stages[2];
-    memset(stages, 0, sizeof(stages));
-    stages[0].bufs[HTN_BUF_WS] = stages[1].bufs[HTN_BUF_WS] = ws.ptr();
-    int ns = 0;
-    if (ap->has_z) {
-        stages[ns].bufs[BUF_L] = Lbuf[i].ptr();
-        stages[ns].bufs[BUF_Z] = z.ptr();
-        stages[ns].tiles = ap->dz.tiles, stages[ns].segs = ap->dz.segs, stages[ns].n_tiles = ap->dz.ntiles;
-        ++ns;
-    }
-    stages[ns].bufs[BUF_L] = Lbuf[i].ptr();
-    stages[ns].bufs[BUF_R] = Rbuf[i + 2].ptr();
-    stages[ns].bufs[BUF_Z] = z.ptr();
-    stages[ns].tiles = ap->dy.tiles, stages[ns].segs = ap->dy.segs, stages[ns].n_tiles = ap->dy.ntiles;
-    ++ns;
-    if (o.profile) be->sync();
-    const double t_plan = now() - t0;
-    double E = 0.0, res = 0.0, mv_ms = 0.0;
-    int nmv = 0;
+    const int ns = apply_stages(*s.ap, Lbuf[i], Rbuf[i + 2], w.z, stages);
+    if (ns < 0) return 1;
+    clk.plan = clk.lap();
     const bool shard = ctx->shard;
     int n_frozen = 0;
-    DView Qb;
     if (!orth.empty() && optimise) {
         // orthogonalised update: p_k = <phi_k| carried into this bond's bases, one row each; Gram-Schmidt (rows that depend on
         // the ones before them are dropped); then the lowest eigenpair of H_eff inside the complement of those rows
         const int na = (int)orth.size();
         if (kd + na > 31)
             return set_error("htn_bond_update: krylovdim + attached states = %d + %d > 31 (row limit of the projected Lanczos step)", kd, na);
-        Qb = zalloc((int64_t)na * n, false);
-        if (!Qb.base) return set_error("device allocation of the projector rows failed");
+        w.Qb = zalloc((int64_t)na * n, false);
+        if (!w.Qb.base) return set_error("device allocation of the projector rows failed");
         for (int k = 0; k < na; ++k)
-            if (ovl_project(orth[k], i, tl, Qb.ptr() + (int64_t)k * n)) return 1;
-        if (be->orthonormalise_rows(Qb.ptr(), n, na, 1e-12, &n_frozen)) return 1;
+            if (ovl_project(orth[k], i, tl, w.Qb.ptr() + (int64_t)k * n)) return 1;
+        if (be->orthonormalise_rows(w.Qb.ptr(), n, na, 1e-12, &n_frozen)) return 1;
         orth_dropped = na - n_frozen;
     }
     if (n_frozen > 0) {
-        if (be->lanczos_orth(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, o.lanczos_tol, o.maxrestart, shard ? 1 : 0,
-                             shard ? exchange_tramp : nullptr, ctx, Qb.ptr(), n_frozen, &E, &nmv, &res, be->timing ? &mv_ms : nullptr))
+        if (be->lanczos_orth(stages, ns, BUF_X, BUF_Y, w.V.ptr(), n, kd, o.lanczos_tol, o.maxrestart, shard ? 1 : 0,
+                             shard ? exchange_tramp : nullptr, ctx, w.Qb.ptr(), n_frozen, &s.E, &s.nmv, &s.res,
+                             be->timing ? &s.mv_ms : nullptr))
             return 1;
-    } else if (be->lanczos(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, shard ? 1 : 0,
-                           shard ? exchange_tramp : nullptr, ctx, &E, &nmv, &res, be->timing ? &mv_ms : nullptr))
+    } else if (be->lanczos(stages, ns, BUF_X, BUF_Y, w.V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, shard ? 1 : 0,
+                           shard ? exchange_tramp : nullptr, ctx, &s.E, &s.nmv, &s.res, be->timing ? &s.mv_ms : nullptr))
         return 1;
-    if (o.profile) be->sync();
-    const double t_lan = now() - t0 - t_plan;
-    cplx* x = V.ptr();
-    // ---- SVD + truncation ----
-    auto sc = cached<SvdC>(std::string(right ? "svdR" : "svdL") + bl->key + "|" + br->key, [&]() -> std::shared_ptr<SvdC> {
+    clk.lanczos = clk.lap();
+    return 0;
+}
+
+// compiled SVD of the theta layout: staging items and block descriptors on the device; with more than one rank also the
+// lists of the blocks this rank owns
+std::shared_ptr<SvdC> htn_mps::make_svd(int i, const ThetaLayout& tl, bool right) {
+    return cached<SvdC>(std::string(right ? "svdR" : "svdL") + bonds[i]->key + "|" + bonds[i + 2]->key, [&]() -> std::shared_ptr<SvdC> {
         auto s = std::make_shared<SvdC>();
         if (plan_svd(tl, right, s->sp)) return nullptr;
-        s->stage = dalloc(sizeof(htn_copy_item) * s->sp.stage.size());
-        s->desc = dalloc(sizeof(htn_svd_block) * s->sp.desc.size());
-        if (!s->stage || !s->desc) return nullptr;
-        if (be->upload(s->stage->p, s->sp.stage.data(), sizeof(htn_copy_item) * s->sp.stage.size())) return nullptr;
-        if (be->upload(s->desc->p, s->sp.desc.data(), sizeof(htn_svd_block) * s->sp.desc.size())) return nullptr;
+        if (!(s->stage = upload_vec(be, s->sp.stage)) || !(s->desc = upload_vec(be, s->sp.desc))) return nullptr;
         if (ctx->world > 1) {
             // owner of every block: longest first onto the least loaded rank (deterministic: every rank computes the same map)
             const int nbk = (int)s->sp.mids.size();
@@ -823,45 +896,47 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
                 }
             }
             s->n_own = (int)s->own_desc.size();
-            if (s->n_own) {
-                s->own_stage = dalloc(sizeof(htn_copy_item) * st_own.size());
-                s->own_desc_dev = dalloc(sizeof(htn_svd_block) * s->own_desc.size());
-                if (!s->own_stage || !s->own_desc_dev) return nullptr;
-                if (be->upload(s->own_stage->p, st_own.data(), sizeof(htn_copy_item) * st_own.size())) return nullptr;
-                if (be->upload(s->own_desc_dev->p, s->own_desc.data(), sizeof(htn_svd_block) * s->own_desc.size())) return nullptr;
-            }
+            if (s->n_own && (!(s->own_stage = upload_vec(be, st_own)) || !(s->own_desc_dev = upload_vec(be, s->own_desc)))) return nullptr;
         }
         return s;
     });
-    if (!sc) return 1;
-    const SvdPlan& sp = sc->sp;
+}
+
+// SVD: stage the optimised theta block by block, Jacobi, ONE download (singular values + per-block sweep counts share a
+// buffer: one device-to-host copy, one stream sync per bond), convergence check
+int htn_mps::bond_svd(int i, bool right, const htn_sweep_opts& o, BondWork& w) {
+    w.sc = make_svd(i, *w.tl, right);
+    if (!w.sc) return 1;
+    const SvdC& sc = *w.sc;
+    const SvdPlan& sp = sc.sp;
     const int nb = (int)sp.mids.size();
-    DView G = zalloc(sp.g_size, false), Vj = zalloc(sp.v_size, false);
-    // singular values and per-block sweep counts share one buffer: ONE device-to-host copy (one stream sync) per bond
-    const size_t s_elems = ((size_t)std::max<int64_t>(sp.s_size, 1) + 1) & ~(size_t)1, i_elems = (size_t)std::max(nb, 1);
-    DBufP S = dalloc(sizeof(double) * s_elems + sizeof(int32_t) * i_elems);
-    if (!G.base || !Vj.base || !S) return set_error("device allocation failed (SVD workspace)");
-    int32_t* info_dev = (int32_t*)((double*)S->p + s_elems);
+    w.G = zalloc(sp.g_size, false), w.Vj = zalloc(sp.v_size, false);
+    w.s_elems = ((size_t)std::max<int64_t>(sp.s_size, 1) + 1) & ~(size_t)1;
+    const size_t s_elems = w.s_elems, i_elems = (size_t)std::max(nb, 1);
+    const size_t s_bytes = sizeof(double) * s_elems + sizeof(int32_t) * i_elems;
+    w.S = dalloc(s_bytes);
+    if (!w.G.base || !w.Vj.base || !w.S) return set_error("device allocation failed (SVD workspace)");
+    int32_t* info_dev = (int32_t*)((double*)w.S->p + s_elems);
     // Sector-sharded SVD (world > 1): every rank stages and decomposes only the blocks it owns; everything else
     // in G / S (and the rotation workspace of accumulate-mode blocks) stays zero and ONE sum over ranks per buffer
     // hands every rank the complete result -- bit-identical everywhere (x + 0 + ... + 0), so the ranks stay in lock step.
     const bool svd_shard = ctx->world > 1 && ctx->shard;
+    const DBufP& stage = svd_shard ? sc.own_stage : sc.stage;
+    const DBufP& desc_dev = svd_shard ? sc.own_desc_dev : sc.desc;
+    const htn_svd_block* desc_host = svd_shard ? sc.own_desc.data() : sp.desc.data();
+    const int n_run = svd_shard ? sc.n_own : nb;               // (sharded: may be 0, then this rank only takes part in the sums)
+    const bool run = n_run > 0 || !svd_shard;
     if (svd_shard) {
-        if (be->zero(G.ptr(), sizeof(cplx) * (size_t)std::max<int64_t>(sp.g_size, 1))) return 1;
-        if (be->zero(S->p, sizeof(double) * s_elems + sizeof(int32_t) * i_elems)) return 1;
-        if (sp.any_accumulate && be->zero(Vj.ptr(), sizeof(cplx) * (size_t)std::max<int64_t>(sp.v_size, 1))) return 1;
-        if (sc->n_own && be->batched_copy(G.ptr(), x, nullptr, nullptr, (const htn_copy_item*)sc->own_stage->p, sc->n_own, 1.0)) return 1;
-    } else if (be->batched_copy(G.ptr(), x, nullptr, nullptr, (const htn_copy_item*)sc->stage->p, nb, 1.0))
-        return 1;
+        if (be->zero(w.G.ptr(), sizeof(cplx) * (size_t)std::max<int64_t>(sp.g_size, 1))) return 1;
+        if (be->zero(w.S->p, s_bytes)) return 1;
+        if (sp.any_accumulate && be->zero(w.Vj.ptr(), sizeof(cplx) * (size_t)std::max<int64_t>(sp.v_size, 1))) return 1;
+    }
+    if (run && be->batched_copy(w.G.ptr(), w.V.ptr(), nullptr, nullptr, (const htn_copy_item*)stage->p, n_run, 1.0)) return 1;
     // Singular directions far below what the truncation keeps need not be resolved (optional, OFF by default).
     // truncbelow(eta): everything below eta goes anyway.  truncdim(D): if the previous update of this bond (same D) was
     // limited by D, its smallest kept value is where the cut will fall again.  x is normalised: values compare across sweeps.
-    htn_svd_opts so;
     int32_t jac_used = 0;
-    so.split_elems = o.svd_split_elems;
-    so.sweeps_hint = 0;
-    so.rank_cut = 0.0;
-    so.sweeps_used = &jac_used;
+    htn_svd_opts so = {o.svd_split_elems, 0, 0.0, &jac_used};      // split_elems, sweeps_hint, rank_cut, sweeps_used
     {       // the previous update of this bond tells how many outer sweeps the large blocks will need (speculation bound)
         auto h = sweeps_hint.find(i + 1);
         if (h != sweeps_hint.end()) so.sweeps_hint = h->second;
@@ -873,78 +948,84 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
             cut = o.rank_cut * h->second.second;
         so.rank_cut = std::max(cut, o.rank_cut * o.cutoff);
     }
-    if (svd_shard) {
-        if (sc->n_own && be->jacobi_svd(G.ptr(), Vj.ptr(), (double*)S->p, (const htn_svd_block*)sc->own_desc_dev->p,
-                                        sc->own_desc.data(), sc->n_own, sp.max_m, o.jacobi_max_sweeps > 0 ? o.jacobi_max_sweeps : 40,
-                                        o.jacobi_tol > 0.0 ? o.jacobi_tol : 1e-14, info_dev, &so))
-            return 1;
-        if (exchange_tramp(G.ptr(), std::max<int64_t>(sp.g_size, 1), ctx)) return set_error("sharded SVD: exchange of the blocks failed");
-        if (exchange_tramp(S->p, (int64_t)(s_elems / 2), ctx)) return set_error("sharded SVD: exchange of the singular values failed");
-        if (sp.any_accumulate && exchange_tramp(Vj.ptr(), std::max<int64_t>(sp.v_size, 1), ctx)) return 1;
-    } else if (be->jacobi_svd(G.ptr(), Vj.ptr(), (double*)S->p, (const htn_svd_block*)sc->desc->p, sp.desc.data(), nb, sp.max_m,
-                              o.jacobi_max_sweeps > 0 ? o.jacobi_max_sweeps : 40, o.jacobi_tol > 0.0 ? o.jacobi_tol : 1e-14,
-                              info_dev, &so))
+    if (run && be->jacobi_svd(w.G.ptr(), w.Vj.ptr(), (double*)w.S->p, (const htn_svd_block*)desc_dev->p, desc_host, n_run, sp.max_m,
+                              o.jacobi_max_sweeps, o.jacobi_tol, info_dev, &so))
         return 1;
-    if (jac_used > 0) sweeps_hint[i + 1] = jac_used;
-    static const bool dbg_timers = getenv("HTN_DEBUG_HOST_TIMERS") != nullptr;
-    const double tA = now();
-    std::vector<double> s_host(s_elems + (i_elems + 1) / 2);
-    if (be->download(s_host.data(), S->p, sizeof(double) * s_elems + sizeof(int32_t) * i_elems)) return 1;
-    const double tB = now();
-    const int32_t* info_h = (const int32_t*)(s_host.data() + s_elems);
-    int jac_sweeps = 0;
-    for (int b = 0; b < (svd_shard ? sc->n_own : nb); ++b) {        // (sharded: the counts of this rank's own blocks)
-        if (info_h[b] < 0) return set_error("Jacobi SVD did not converge (bond %d, block %d, %d sweeps)", i + 1, b, -info_h[b]);
-        jac_sweeps = std::max(jac_sweeps, (int)info_h[b]);
+    if (svd_shard) {
+        if (exchange_tramp(w.G.ptr(), std::max<int64_t>(sp.g_size, 1), ctx)) return set_error("sharded SVD: exchange of the blocks failed");
+        if (exchange_tramp(w.S->p, (int64_t)(s_elems / 2), ctx)) return set_error("sharded SVD: exchange of the singular values failed");
+        if (sp.any_accumulate && exchange_tramp(w.Vj.ptr(), std::max<int64_t>(sp.v_size, 1), ctx)) return 1;
     }
-    // per-block descending order (ties: original column index ascending) and the global truncation
-    std::vector<int> lens(nb), qd(nb);
-    std::vector<std::vector<int>> order(nb);
-    std::vector<double> vals;
-    vals.reserve((size_t)sp.s_size);
+    if (jac_used > 0) sweeps_hint[i + 1] = jac_used;
+    w.tA = now();
+    w.s_host.resize(s_elems + (i_elems + 1) / 2);
+    if (be->download(w.s_host.data(), w.S->p, s_bytes)) return 1;
+    w.tB = now();
+    const int32_t* info_h = (const int32_t*)(w.s_host.data() + s_elems);
+    for (int b = 0; b < n_run; ++b) {                          // (sharded: the counts of this rank's own blocks)
+        if (info_h[b] < 0) return set_error("Jacobi SVD did not converge (bond %d, block %d, %d sweeps)", i + 1, b, -info_h[b]);
+        w.jac_sweeps = std::max(w.jac_sweeps, (int)info_h[b]);
+    }
+    return 0;
+}
+
+// truncate (host only): per-block descending order (ties: original column index ascending), the global truncation rule,
+// the new middle bond, the hint for the next visit of this bond
+int htn_mps::bond_truncate(int i, const htn_sweep_opts& o, BondWork& w) {
+    const SvdPlan& sp = w.sc->sp;
+    const int nb = (int)sp.mids.size();
+    w.lens.resize(nb), w.qd.resize(nb), w.order.resize(nb);
+    w.vals.reserve((size_t)sp.s_size);
     std::vector<std::pair<double, int>> tmp;
     for (int b = 0; b < nb; ++b) {
         const int len = sp.desc[b].n;
-        const double* sv = s_host.data() + sp.desc[b].s_off;
-        lens[b] = len;
-        qd[b] = sym.qdim(sp.mids[b]);
+        const double* sv = w.s_host.data() + sp.desc[b].s_off;
+        w.lens[b] = len;
+        w.qd[b] = mpo->sym.qdim(sp.mids[b]);
         tmp.resize(len);
         for (int k = 0; k < len; ++k) tmp[k] = {sv[k], k};
         std::sort(tmp.begin(), tmp.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& c) {
             return a.first != c.first ? a.first > c.first : a.second < c.second;
         });
-        order[b].resize(len);
+        w.order[b].resize(len);
         for (int k = 0; k < len; ++k) {
-            order[b][k] = tmp[k].second;
-            vals.push_back(tmp[k].first);
+            w.order[b][k] = tmp[k].second;
+            w.vals.push_back(tmp[k].first);
         }
     }
-    std::vector<int> counts;
-    double tw = 0.0, nrm = 0.0;
-    truncate(vals, lens, qd, o.chi_full, o.cutoff, o.weighting, counts, tw, nrm);
+    truncate(w.vals, w.lens, w.qd, o.chi_full, o.cutoff, o.weighting, w.counts, w.tw, w.nrm);
     std::vector<std::pair<Sec, int>> mid_items;
     int64_t kept_tot = 0, positive = 0;
     for (int b = 0; b < nb; ++b) {
-        if (counts[b] > 0) mid_items.push_back({sp.mids[b], counts[b]});
-        kept_tot += counts[b];
+        if (w.counts[b] > 0) mid_items.push_back({sp.mids[b], w.counts[b]});
+        kept_tot += w.counts[b];
     }
-    for (double v : vals) positive += v > 0.0;
-    if (kept_tot == 0 || !(nrm > 0.0)) return set_error("htn_bond_update: nothing kept by the truncation on bond %d", i + 1);
-    BondP mid = std::make_shared<Bond>(mid_items);
-    const double tC = now();
+    for (double v : w.vals) positive += v > 0.0;
+    if (kept_tot == 0 || !(w.nrm > 0.0)) return set_error("htn_bond_update: nothing kept by the truncation on bond %d", i + 1);
+    w.mid = std::make_shared<Bond>(mid_items);
+    w.tC = now();
     // hint for the next visit of this bond: the smallest kept value, valid only if the dimension limit (not the number
     // of available states) ended the kept set
-    if (o.chi_full > 0 && tw > 0.0 && kept_tot < positive) {
+    if (o.chi_full > 0 && w.tw > 0.0 && kept_tot < positive) {
         double smin = 1e300;
         size_t p = 0;
         for (int b = 0; b < nb; ++b) {
-            if (counts[b] > 0) smin = std::min(smin, vals[p + counts[b] - 1]);
-            p += lens[b];
+            if (w.counts[b] > 0) smin = std::min(smin, w.vals[p + w.counts[b] - 1]);
+            p += w.lens[b];
         }
         cut_hint[i + 1] = {{o.chi_full, o.cutoff}, smin};
     } else
         cut_hint.erase(i + 1);
-    // the finalisation plan depends on the kept COUNTS only (not on which columns carry them): memoised
+    return 0;
+}
+
+// finalise: the copy items of the kept counts (memoised: the plan depends on the COUNTS only, not on which columns carry
+// them), gather of the kept columns into the two site tensors, the centre GEMM, store sites and bond
+int htn_mps::bond_finalise(int i, bool right, BondWork& w) {
+    const ThetaLayout& tl = *w.tl;
+    const SvdPlan& sp = w.sc->sp;
+    const std::vector<int>& counts = w.counts;
+    const BondP bl = bonds[i], br = bonds[i + 2], mid = w.mid;
     std::string ckey((const char*)counts.data(), sizeof(int) * counts.size());
     auto fc = cached<FinC>(std::string(right ? "finR" : "finL") + bl->key + "|" + br->key + "|" + ckey, [&]() -> std::shared_ptr<FinC> {
         auto f = std::make_shared<FinC>();
@@ -953,14 +1034,12 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
         FinalizePlan fp;
         plan_finalize(tl, sp, counts, *f->layA, *f->layB, right, 0, f->layA->size, fp);
         f->n_ig = (int)fp.iso_g.size(), f->n_cg = (int)fp.cen_g.size(), f->n_iv = (int)fp.iso_v.size();
-        const size_t tot = (size_t)(f->n_ig + f->n_cg + f->n_iv);
-        if (tot) {
+        if (f->n_ig + f->n_cg + f->n_iv) {
             std::vector<htn_copy_item> all;
             all.insert(all.end(), fp.iso_g.begin(), fp.iso_g.end());
             all.insert(all.end(), fp.cen_g.begin(), fp.cen_g.end());
             all.insert(all.end(), fp.iso_v.begin(), fp.iso_v.end());
-            f->items = dalloc(sizeof(htn_copy_item) * tot);
-            if (!f->items || be->upload(f->items->p, all.data(), sizeof(htn_copy_item) * tot)) return nullptr;
+            if (!(f->items = upload_vec(be, all))) return nullptr;
             f->ig = (const htn_copy_item*)f->items->p;
             f->cg = f->ig + f->n_ig;
             f->iv = f->cg + f->n_cg;
@@ -970,22 +1049,23 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
         return f;
     });
     if (!fc) return 1;
-    const double tD = now();
+    w.tD = now();
     idx_host.clear();
-    for (int b = 0; b < nb; ++b)
-        for (int k = 0; k < counts[b]; ++k) idx_host.push_back(order[b][k]);
-    DBufP idx_d = dalloc(sizeof(int32_t) * std::max<size_t>(idx_host.size(), 1));
+    for (size_t b = 0; b < counts.size(); ++b)
+        for (int k = 0; k < counts[b]; ++k) idx_host.push_back(w.order[b][k]);
+    w.idx = upload_vec(be, idx_host);
     const int64_t sizeA = fc->layA->size, sizeB = fc->layB->size;
     DView out = zalloc(sizeA + sizeB, true);
-    if (!idx_d || !out.base) return set_error("device allocation failed (site tensors)");
-    if (be->upload(idx_d->p, idx_host.data(), sizeof(int32_t) * idx_host.size())) return 1;
-    const int32_t* idxp = (const int32_t*)idx_d->p;
-    const double* Sp = (const double*)S->p;
-    if (fc->n_ig && be->batched_copy(out.ptr(), G.ptr(), idxp, Sp, fc->ig, fc->n_ig, 1.0)) return 1;
-    if (fc->n_cg && be->batched_copy(out.ptr(), G.ptr(), idxp, Sp, fc->cg, fc->n_cg, 1.0 / nrm)) return 1;
-    if (fc->n_iv && be->batched_copy(out.ptr(), Vj.ptr(), idxp, Sp, fc->iv, fc->n_iv, 1.0)) return 1;
+    if (!w.idx || !out.base) return set_error("device allocation failed (site tensors)");
+    const int32_t* idxp = (const int32_t*)w.idx->p;
+    const double* Sp = (const double*)w.S->p;
+    cplx* x = w.V.ptr();
+    const int64_t n = tl.size;
+    if (fc->n_ig && be->batched_copy(out.ptr(), w.G.ptr(), idxp, Sp, fc->ig, fc->n_ig, 1.0)) return 1;
+    if (fc->n_cg && be->batched_copy(out.ptr(), w.G.ptr(), idxp, Sp, fc->cg, fc->n_cg, 1.0 / w.nrm)) return 1;
+    if (fc->n_iv && be->batched_copy(out.ptr(), w.Vj.ptr(), idxp, Sp, fc->iv, fc->n_iv, 1.0)) return 1;
     if (fc->has_cen) {
-        if (be->scale(x, n, 1.0 / nrm)) return 1;               // centre = U^H (M / nrm)
+        if (be->scale(x, n, 1.0 / w.nrm)) return 1;             // centre = U^H (M / nrm)
         if (gemm(fc->cen, {{BUF_X, x}, {BUF_S1, out.ptr()}, {BUF_Y, out.ptr()}})) return 1;
     }
     bonds[i + 1] = mid;
@@ -993,59 +1073,58 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
     site_buf[i] = DView{out.base, out.off};
     site_lay[i + 1] = fc->layB;
     site_buf[i + 1] = DView{out.base, out.off + sizeA};
-    if (dbg_timers)
-        fprintf(stderr, "bond %d: svd call %.1f us, download %.1f, sort+truncate %.1f, finalize plan %.1f, enqueue %.1f  misses %lld hits %lld nvals %zu\n", i + 1,
-                (tA - t0 - t_plan - t_lan) * 1e6, (tB - tA) * 1e6, (tC - tB) * 1e6, (tD - tC) * 1e6, (now() - tD) * 1e6, (long long)misses, (long long)hits, vals.size());
-    if (o.profile) be->sync();
-    const double t_svd = now() - t0 - t_plan - t_lan;
+    return 0;
+}
+
+// advance: the H environment across the site that became an isometry, and the overlap environments of attached states
+// with it (non-optimising moves too)
+int htn_mps::bond_advance(int i, bool right) {
     if (right ? left_env(i) : right_env(i + 1)) return 1;
-    for (auto& os : orth)          // the overlap environments move with the H environment (non-optimising moves too)
-        if (right ? ovl_left(os.phi, i, os.Llay[i], os.Lbuf[i], &os.Llay[i + 1], &os.Lbuf[i + 1])
-                  : ovl_right(os.phi, i + 1, os.Rlay[i + 2], os.Rbuf[i + 2], &os.Rlay[i + 1], &os.Rbuf[i + 1]))
+    for (auto& os : orth)
+        if (right ? ovl_step('L', os.phi, i, os.Llay[i], os.Lbuf[i], &os.Llay[i + 1], &os.Lbuf[i + 1])
+                  : ovl_step('R', os.phi, i + 1, os.Rlay[i + 2], os.Rbuf[i + 2], &os.Rlay[i + 1], &os.Rbuf[i + 1]))
             return 1;
-    if (o.profile) be->sync();
-    const double t_env = now() - t0 - t_plan - t_lan - t_svd;
-    energy = E;
-    centre = right ? i + 1 : i;
+    return 0;
+}
+
+// Schmidt spectrum of the new middle bond: the kept values of the normalised state, per sector
+void htn_mps::bond_spectrum(int i, const BondWork& w) {
+    const SvdPlan& sp = w.sc->sp;
     Spectrum spec;
-    {
-        size_t p = 0;
-        for (int b = 0; b < nb; ++b) {
-            if (counts[b] > 0) {
-                spec.secs.push_back(sp.mids[b]);
-                std::vector<double> v(counts[b]);
-                const double f = 1.0 / nrm / sqrt((double)qd[b]);
-                for (int k = 0; k < counts[b]; ++k) v[k] = vals[p + k] * f;
-                spec.vals.push_back(std::move(v));
-            }
-            p += lens[b];
+    size_t p = 0;
+    for (size_t b = 0; b < w.counts.size(); ++b) {
+        if (w.counts[b] > 0) {
+            spec.secs.push_back(sp.mids[b]);
+            std::vector<double> v(w.counts[b]);
+            const double f = 1.0 / w.nrm / sqrt((double)w.qd[b]);
+            for (int k = 0; k < w.counts[b]; ++k) v[k] = w.vals[p + k] * f;
+            spec.vals.push_back(std::move(v));
         }
+        p += w.lens[b];
     }
     spectra[i + 1] = std::move(spec);
-    if (st) {
-        memset(st, 0, sizeof(*st));
-        st->bond = i + 1;
-        st->direction = direction;
-        st->n_matvec = nmv;
-        st->jacobi_sweeps = jac_sweeps;
-        st->chi_full = (int32_t)mid->dim_full(sym);
-        st->multiplets = mid->multiplets();
-        st->n_tiles = ap->ntiles;
-        st->n_segs = ap->nsegs;
-        st->theta_size = n;
-        st->apply_flops = ap->flops;
-        st->apply_bytes = 16 * (2 * n + Llay[i]->size + Rlay[i + 2]->size);
-        st->svd_flops = sp.flops;
-        st->energy = E;
-        st->residual = res;
-        st->trunc_weight = tw;
-        st->t_plan = t_plan;
-        st->t_lanczos = t_lan;
-        st->t_svd = t_svd;
-        st->t_env = t_env;
-        st->t_total = now() - t0;
-        st->matvec_ms = mv_ms > 0.0 ? mv_ms : 0.0;      // (0: none of this solve's launches fell on the 1-in-8 timing sample)
-    }
+}
+
+int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st) {
+    if (i < 0 || i + 1 >= L) return set_error("htn_bond_update: bond index %d out of range", i);
+    StageClock clk(be, o.profile);
+    BondWork w;
+    if (bond_solve(i, optimise, o, clk, w)) return 1;          // (laps clk.plan and clk.lanczos)
+    const double t_svd0 = clk.last;
+    if (bond_svd(i, right, o, w)) return 1;
+    if (bond_truncate(i, o, w)) return 1;
+    if (bond_finalise(i, right, w)) return 1;
+    static const bool dbg_timers = getenv("HTN_DEBUG_HOST_TIMERS") != nullptr;
+    if (dbg_timers)
+        fprintf(stderr, "bond %d: svd call %.1f us, download %.1f, sort+truncate %.1f, finalize plan %.1f, enqueue %.1f  misses %lld hits %lld nvals %zu\n", i + 1,
+                (w.tA - t_svd0) * 1e6, (w.tB - w.tA) * 1e6, (w.tC - w.tB) * 1e6, (w.tD - w.tC) * 1e6, (now() - w.tD) * 1e6, (long long)misses, (long long)hits, w.vals.size());
+    clk.svd = clk.lap();
+    if (bond_advance(i, right)) return 1;
+    clk.env = clk.lap();
+    energy = w.sol.E;
+    centre = right ? i + 1 : i;
+    bond_spectrum(i, w);
+    if (st) fill_stats(st, i + 1, direction, w.sol, Llay[i]->size + Rlay[i + 2]->size, w.jac_sweeps, w.sc->sp.flops, w.tw, clk);
     return 0;
 }
 
@@ -1067,40 +1146,6 @@ int htn_mps::sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E) {
 // sqrt(2S_r + 1) in both layout kinds and right tensors sqrt((2S_r + 1) / (2S_l + 1)), so R (carrying sqrt(2S_c + 1))
 // times B_{i+1} and A_{i-1} times L are centres again and Q is orthonormal in the plain sense.
 // =====================================================================================================================
-std::shared_ptr<ApplyC> htn_mps::make_apply1(int i, const SiteLayout& lay) {
-    return cached<ApplyC>(ikey("apply1", i) + lay.kind + bonds[i]->key + "|" + bonds[i + 1]->key, [&]() -> std::shared_ptr<ApplyC> {
-        ApplyPlan p;
-        plan_apply1(*mpo, lay, *Llay[i], *Rlay[i + 1], mpo->sites[i], p);
-        auto a = std::make_shared<ApplyC>();
-        a->has_z = p.has_z;
-        a->zsize = p.zsize;
-        a->flops = p.ty.flops + (p.has_z ? p.tz.flops : 0);
-        a->ntiles = p.ty.ntiles + (p.has_z ? p.tz.ntiles : 0);
-        a->nsegs = p.ty.nsegs + (p.has_z ? p.tz.nsegs : 0);
-        if (p.has_z && upload_tasks(p.tz, a->dz)) return nullptr;
-        if (upload_tasks(p.ty, a->dy)) return nullptr;
-        return a;
-    });
-}
-
-int htn_mps::heff1_stages(int i, const ApplyC& ap, const DView& z, htn_gemm_launch* stages) {
-    if (ensure_ws(std::max(ap.dy.ws_slots, ap.has_z ? ap.dz.ws_slots : 0))) return -1;
-    memset(stages, 0, 2 * sizeof(htn_gemm_launch));
-    stages[0].bufs[HTN_BUF_WS] = stages[1].bufs[HTN_BUF_WS] = ws.ptr();
-    int ns = 0;
-    if (ap.has_z) {
-        stages[ns].bufs[BUF_L] = Lbuf[i].ptr();
-        stages[ns].bufs[BUF_Z] = z.ptr();
-        stages[ns].tiles = ap.dz.tiles, stages[ns].segs = ap.dz.segs, stages[ns].n_tiles = ap.dz.ntiles;
-        ++ns;
-    }
-    stages[ns].bufs[BUF_L] = Lbuf[i].ptr();
-    stages[ns].bufs[BUF_R] = Rbuf[i + 1].ptr();
-    stages[ns].bufs[BUF_Z] = z.ptr();
-    stages[ns].tiles = ap.dy.tiles, stages[ns].segs = ap.dy.segs, stages[ns].n_tiles = ap.dy.ntiles;
-    return ns + 1;
-}
-
 // dst (layout `to`) = src (layout `from`), block by block: the two kinds hold the same (l, s, r) blocks with the same values
 int htn_mps::relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst) {
     auto rc = cached<RelayC>(std::string("relay") + from.kind + to.kind + from.bl->key + "|" + from.br->key, [&]() -> std::shared_ptr<RelayC> {
@@ -1110,17 +1155,11 @@ int htn_mps::relay(const SiteLayout& from, const cplx* src, const SiteLayout& to
             const int sq = from.block({k[0], k[1]}, k[2], {k[3], k[4]});
             if (sq < 0) continue;
             const BlockRec &D = to.blocks[q], &S = from.blocks[sq];
-            htn_copy_item it;
-            memset(&it, 0, sizeof(it));
-            it.dst_off = D.off, it.src_off = S.off, it.idx_off = -1, it.scl_off = -1;
-            it.rows = D.m, it.cols = D.n, it.ldd = D.ld, it.lds = S.ld;
-            it.op = HTN_OP_N, it.gather_dim = 0, it.scale_dim = -1, it.inv_norm = 0;
-            items.push_back(it);
+            items.push_back(copy_item(D.off, D.ld, S.off, S.ld, D.m, D.n));
         }
         auto r = std::make_shared<RelayC>();
         r->n = (int)items.size();
-        r->items = dalloc(sizeof(htn_copy_item) * std::max<size_t>(items.size(), 1));
-        if (!r->items || be->upload(r->items->p, items.data(), sizeof(htn_copy_item) * items.size())) return nullptr;
+        if (!(r->items = upload_vec(be, items))) return nullptr;
         return r;
     });
     if (!rc) return 1;
@@ -1143,11 +1182,11 @@ int htn_mps::update_site(int i, int direction, bool optimise, const htn_sweep_op
     if (direction < -1 || direction > 1) return set_error("htn_site_update: direction %d (must be -1, 0 or +1)", direction);
     if ((direction > 0 && i + 1 >= L) || (direction < 0 && i == 0))
         return set_error("htn_site_update: site %d has no neighbour in direction %d", i, direction);
-    const double t0 = now();
-    const Sym& sym = mpo->sym;
+    StageClock clk(be, o.profile);
     const SiteLayoutP cur = site_lay[i];
     const SiteLayoutP lay = direction == 0 ? cur : site_layout(direction > 0 ? 'L' : 'R', bonds[i], bonds[i + 1]);
-    const int64_t n = lay->size;
+    Solve s;
+    const int64_t n = s.n = lay->size;
     if (n <= 0) return set_error("htn_site_update: empty site tensor on site %d", i);
     for (const auto& M : lay->mats)      // a full-rank gauge move needs the long side along the orthonormal direction
         if (direction != 0 && (lay->kind == 'L' ? M.rows < M.cols : M.cols < M.rows))
@@ -1155,31 +1194,26 @@ int htn_mps::update_site(int i, int direction, bool optimise, const htn_sweep_op
                              "site supports: run a two-site sweep first", M.c.N, M.c.j, i, M.rows, M.cols);
     if (direction != 0 && site_lay[i + direction]->kind != (direction > 0 ? 'R' : 'L'))
         return set_error("htn_site_update: site %d is not in %s layout", i + direction, direction > 0 ? "right" : "left");
-    const int kd = o.krylovdim > 0 ? o.krylovdim : 30;
+    const int kd = o.krylovdim;
     DView V = zalloc((int64_t)(kd + 2) * n, false);
     if (!V.base) return set_error("device allocation of the Krylov basis failed (%lld elements)", (long long)((kd + 2) * n));
     if (relay(*cur, site_buf[i].ptr(), *lay, V.ptr())) return 1;
-    auto ap = make_apply1(i, *lay);
-    if (!ap) return 1;
-    DView z = zalloc(ap->zsize, false);
+    s.ap = make_apply1(i, *lay);
+    if (!s.ap) return 1;
+    DView z = zalloc(s.ap->zsize, false);
     if (!z.base) return set_error("device allocation failed (one-site apply)");
     htn_gemm_launch stages[2];
-    const int ns = heff1_stages(i, *ap, z, stages);
+    const int ns = apply_stages(*s.ap, Lbuf[i], Rbuf[i + 1], z, stages);
     if (ns < 0) return 1;
-    if (o.profile) be->sync();
-    const double t_plan = now() - t0;
-    double E = 0.0, res = 0.0, mv_ms = 0.0;
-    int nmv = 0;
-    if (be->lanczos(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, 0, nullptr, ctx, &E, &nmv,
-                    &res, be->timing ? &mv_ms : nullptr))
+    clk.plan = clk.lap();
+    if (be->lanczos(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, optimise ? o.lanczos_tol : 1e300, o.maxrestart, 0, nullptr, ctx, &s.E, &s.nmv,
+                    &s.res, be->timing ? &s.mv_ms : nullptr))
         return 1;
-    if (o.profile) be->sync();
-    const double t_lan = now() - t0 - t_plan;
+    clk.lanczos = clk.lap();
     // ---- the optimised centre, then the gauge move ----
     DView out = zalloc(n, false);
     if (!out.base) return set_error("device allocation failed (site tensor)");
     if (relay(*lay, V.ptr(), *lay, out.ptr())) return 1;
-    double t_env = 0.0;
     const int crossed = direction > 0 ? i + 1 : i;
     if (direction != 0) {
         const int j = i + direction;
@@ -1190,10 +1224,7 @@ int htn_mps::update_site(int i, int direction, bool optimise, const htn_sweep_op
                                       auto g = std::make_shared<Gauge1C>();
                                       Tasks t;
                                       plan_gauge1(*lay, *nl, g->desc, g->rsize, t);
-                                      g->desc_dev = dalloc(sizeof(htn_qr_block) * std::max<size_t>(g->desc.size(), 1));
-                                      if (!g->desc_dev || be->upload(g->desc_dev->p, g->desc.data(), sizeof(htn_qr_block) * g->desc.size()))
-                                          return nullptr;
-                                      if (upload_tasks(t, g->absorb)) return nullptr;
+                                      if (!(g->desc_dev = upload_vec(be, g->desc)) || upload_tasks(t, g->absorb)) return nullptr;
                                       return g;
                                   });
         if (!gc) return 1;
@@ -1205,37 +1236,15 @@ int htn_mps::update_site(int i, int direction, bool optimise, const htn_sweep_op
         site_buf[i] = out;
         site_buf[j] = nb_out;
         centre = j;
-        if (o.profile) be->sync();
-        const double t1 = now();
+        clk.lap();                       // (the QR / LQ and the absorption: t_svd is what the other stages leave of the total)
         if (direction > 0 ? left_env(i) : right_env(i)) return 1;
-        if (o.profile) be->sync();
-        t_env = now() - t1;
+        clk.env = clk.lap();
     } else {
         site_lay[i] = lay;
         site_buf[i] = out;
     }
-    energy = E;
-    if (st) {
-        memset(st, 0, sizeof(*st));
-        st->bond = crossed;
-        st->direction = direction;
-        st->n_matvec = nmv;
-        st->chi_full = (int32_t)bonds[crossed]->dim_full(sym);
-        st->multiplets = bonds[crossed]->multiplets();
-        st->n_tiles = ap->ntiles;
-        st->n_segs = ap->nsegs;
-        st->theta_size = n;
-        st->apply_flops = ap->flops;
-        st->apply_bytes = 16 * (2 * n + Llay[i]->size + Rlay[i + 1]->size);
-        st->energy = E;
-        st->residual = res;
-        st->t_plan = t_plan;
-        st->t_lanczos = t_lan;
-        st->t_env = t_env;
-        st->t_total = now() - t0;
-        st->t_svd = st->t_total - t_plan - t_lan - t_env;       // the QR / LQ and the absorption
-        st->matvec_ms = mv_ms > 0.0 ? mv_ms : 0.0;
-    }
+    energy = s.E;
+    if (st) fill_stats(st, crossed, direction, s, Llay[i]->size + Rlay[i + 1]->size, 0, 0, 0.0, clk);
     return 0;
 }
 
@@ -1483,15 +1492,6 @@ int add_gemm_seg(Tasks& t, int64_t a_off, int lda, int op_a, int64_t b_off, int 
     return t.nsegs - 1;
 }
 
-// device buffer of host data (copy items, scale factors, small matrices)
-template <class T>
-DBufP upload_vec(Backend* be, const std::vector<T>& v) {
-    auto b = std::make_shared<DBuf>(be, sizeof(T) * std::max<size_t>(v.size(), 1));
-    if (!b->p) return nullptr;
-    if (!v.empty() && be->upload(b->p, v.data(), sizeof(T) * v.size())) return nullptr;
-    return b;
-}
-
 }  // namespace
 
 struct htn_idmrg {
@@ -1703,16 +1703,7 @@ int htn_idmrg::predict(const std::vector<BondP>& ob, const std::vector<DView>& A
             const int bi = lay->block(sh(l), key[2], sh(r));
             if (bi < 0) continue;
             const BlockRec &src = al.blocks[q], &dst = lay->blocks[bi];
-            htn_copy_item it;
-            memset(&it, 0, sizeof(it));
-            it.dst_off = dst.off;
-            it.src_off = src.off;
-            it.idx_off = -1;
-            it.rows = dst.m;
-            it.cols = dst.n;
-            it.ldd = dst.ld;
-            it.lds = src.ld;
-            it.op = HTN_OP_N;
+            htn_copy_item it = copy_item(dst.off, dst.ld, src.off, src.ld, dst.m, dst.n);
             it.scale_dim = 0;
             it.scl_off = (int64_t)scl.size();
             const std::vector<double> inv = inv_values(sig[k].at(l));
@@ -2073,14 +2064,7 @@ int htn_heff1_apply(htn_mps* mps, int32_t i, const void* x_host, void* y_host) {
     const SiteLayout& lay = *mps->site_lay[i];
     auto ap = mps->make_apply1(i, lay);
     if (!ap) return 1;
-    const int64_t n = lay.size;
-    DView x = mps->zalloc(n, false), y = mps->zalloc(n, true), z = mps->zalloc(ap->zsize, false);
-    if (!x.base || !y.base || !z.base) return set_error("device allocation failed");
-    if (mps->be->upload(x.ptr(), x_host, sizeof(cplx) * n)) return 1;
-    if (ap->has_z && mps->gemm(ap->dz, {{BUF_X, x.ptr()}, {BUF_L, mps->Lbuf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
-    if (mps->gemm(ap->dy, {{BUF_X, x.ptr()}, {BUF_Y, y.ptr()}, {BUF_L, mps->Lbuf[i].ptr()}, {BUF_R, mps->Rbuf[i + 1].ptr()}, {BUF_Z, z.ptr()}}))
-        return 1;
-    return mps->be->download(y_host, y.ptr(), sizeof(cplx) * n);
+    return mps->apply_once(*ap, mps->Lbuf[i], mps->Rbuf[i + 1], lay.size, x_host, y_host, false);
 }
 // Host-memory statement of the kernel-level entry (Householder reflections): what the CPU baseline library exports.  Weak: in
 // libhubbardtn_hip.so the definition of htn_qr.hip (device pointers, the gfx950 kernel) takes its place at link time.
@@ -2141,7 +2125,7 @@ int htn_mps_overlap(htn_mps* a, const htn_mps* b, double* out_host) {
     for (int i = 0; i < a->L; ++i) {
         OvlLayoutP nl;
         DView nb;
-        if (a->ovl_left(b, i, lay, buf, &nl, &nb)) return 1;
+        if (a->ovl_step('L', b, i, lay, buf, &nl, &nb)) return 1;
         lay = nl;
         buf = nb;
     }
@@ -2172,15 +2156,7 @@ int htn_heff2_apply(htn_mps* mps, int32_t i, const void* x_host, void* y_host) {
     ThetaLayoutP tl = mps->theta_layout(mps->bonds[i], mps->bonds[i + 2]);
     auto ap = mps->make_apply(i, *tl);
     if (!ap) return 1;
-    const int64_t n = tl->size;
-    DView x = mps->zalloc(n, false), y = mps->zalloc(n, true), z = mps->zalloc(ap->zsize, false);
-    if (!x.base || !y.base || !z.base) return set_error("device allocation failed");
-    if (mps->be->upload(x.ptr(), x_host, sizeof(cplx) * n)) return 1;
-    if (ap->has_z && mps->gemm(ap->dz, {{BUF_X, x.ptr()}, {BUF_L, mps->Lbuf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
-    if (mps->gemm(ap->dy, {{BUF_X, x.ptr()}, {BUF_Y, y.ptr()}, {BUF_L, mps->Lbuf[i].ptr()}, {BUF_R, mps->Rbuf[i + 2].ptr()}, {BUF_Z, z.ptr()}}))
-        return 1;
-    if (mps->ctx->shard && exchange_tramp(y.ptr(), n, mps->ctx)) return set_error("htn_heff2_apply: exchange failed");
-    return mps->be->download(y_host, y.ptr(), sizeof(cplx) * n);
+    return mps->apply_once(*ap, mps->Lbuf[i], mps->Rbuf[i + 2], tl->size, x_host, y_host, mps->ctx->shard);
 }
 
 int32_t htn_mps_nsites(const htn_mps* mps) { return mps->L; }
