@@ -40,6 +40,10 @@ QR_DT = np.dtype([("offset", "<i8"), ("m", "<i4"), ("n", "<i4"), ("ld", "<i4"), 
 QR_PANEL, QR_CHUNK, QR_MAX_M = 16, 512, 7664       # HTN_QR_PANEL / HTN_QR_CHUNK / HTN_QR_MAX_M
 assert TILE_DT.itemsize == 64 and SEG_DT.itemsize == 64 and SVD_DT.itemsize == 40 and COPY_DT.itemsize == 64
 assert QR_DT.itemsize == 40
+TRDOT_DT = np.dtype([("a_off", "<i8"), ("b_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("lda", "<i4"), ("ldb", "<i4"),
+                     ("out", "<i4"), ("pad", "<i4", (3,)), ("w_re", "<f8"), ("w_im", "<f8")], align=False)      # htn_trdot_item
+TRDOT_SLOTS = 16                                   # HTN_TRDOT_SLOTS
+assert TRDOT_DT.itemsize == 64
 
 # ---- bond-update / sweep level (ABI 2) ----
 SYM_SU2_U1, SYM_U1_U1, SYM_SU2 = 0, 1, 2
@@ -69,6 +73,23 @@ class Symmetry(C.Structure):
                 ("site_j", C.c_int32 * MAX_SITE)]
 
 
+class SiteOp(C.Structure):
+    """htn_site_op"""
+    _fields_ = [("k", C.c_int32), ("dN", C.c_int32), ("red", C.c_double * (MAX_SITE * MAX_SITE))]
+
+
+class TrdotItem(C.Structure):
+    """htn_trdot_item"""
+    _fields_ = [("a_off", C.c_int64), ("b_off", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("lda", C.c_int32),
+                ("ldb", C.c_int32), ("out", C.c_int32), ("pad", C.c_int32 * 3), ("w_re", C.c_double), ("w_im", C.c_double)]
+
+
+class CorrChannel(C.Structure):
+    """htn_corr_channel"""
+    _fields_ = [("open", SiteOp), ("pass_", SiteOp), ("close", SiteOp), ("onsite", SiteOp), ("has_onsite", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 class SvdOpts(C.Structure):
     """htn_svd_opts"""
     _fields_ = [("split_elems", C.c_int32), ("sweeps_hint", C.c_int32), ("rank_cut", C.c_double),
@@ -96,11 +117,13 @@ class IdmrgStats(C.Structure):
                 ("energy_per_site", C.c_double), ("delta", C.c_double)]
 
 
+assert C.sizeof(SiteOp) == 136 and C.sizeof(TrdotItem) == 64 and C.sizeof(CorrChannel) == 4 * 136 + 8
 assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(IdmrgStats) == 48
 
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
-           "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z"]
+           "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z",
+           "htn_trdots_scratch_elems", "htn_block_trdots_z"]
 # entry points shared by libhubbardtn_hip.so and the CPU baseline library (oracle/cpu_backend)
 ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_ctx_set_timing", "htn_comm_unique_id",
                   "htn_ctx_set_comm", "htn_ctx_set_exchange", "htn_mpo_create", "htn_mpo_destroy", "htn_mps_create",
@@ -111,7 +134,7 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_idmrg_create", "htn_idmrg_destroy", "htn_idmrg_boundary", "htn_idmrg_step", "htn_idmrg_window",
                   "htn_mps_set_orthogonal", "htn_mps_orthogonal_count", "htn_mps_overlap",
                   "htn_site_update", "htn_dmrg1_sweep", "htn_mps_centre", "htn_mps_site_theta_size", "htn_heff1_apply",
-                  "htn_qr_blocks_z"]
+                  "htn_qr_blocks_z", "htn_mps_correlator"]
 
 
 class GemmLaunch(C.Structure):
@@ -161,6 +184,9 @@ def load_library(path: str | None = None):
     lib.htn_lanczos_orth_z.argtypes = [C.POINTER(GemmLaunch), i32, i32, i32, vp, i64, i32, f64, i32, vp, i32,
                                        EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(i32), C.POINTER(f64), C.POINTER(f64),
                                        vp, i32, vp]
+    lib.htn_trdots_scratch_elems.argtypes = [i32]
+    lib.htn_trdots_scratch_elems.restype = i64
+    lib.htn_block_trdots_z.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
     declare_engine(lib)
     for name in EXPORTS + ENGINE_EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
@@ -231,6 +257,7 @@ def declare_engine(lib):
     lib.htn_mps_site_theta_size.restype = i64
     lib.htn_heff1_apply.argtypes = [vp, i32, vp, vp]
     lib.htn_qr_blocks_z.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.htn_mps_correlator.argtypes = [vp, C.POINTER(CorrChannel), vp, C.POINTER(f64)]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

@@ -522,6 +522,33 @@ def double_occupancy(psi):
     return psi.engine.site_occupations()[1]
 
 
+def correlation_function(psi, kind, connected=False):
+    """Hermitian L x L matrix of two-point functions of a finite chain, measured on the device without moving the state:
+    kind "hop": sum_s <c+_is c_js>, "nn": <n_i n_j>, "ss": <S_i . S_j>, "pair": <D+_i D_j>; spinful mode also "hop_up", "hop_dn",
+    "szsz", "s+-", "s-+".  connected=True subtracts <n_i><n_j> ("nn") or <sz_i><sz_j> ("szsz")."""
+    if isinstance(psi, InfiniteMPS):
+        raise NotImplementedError("correlation functions need a chain length: they are measured on a finite chain "
+                                  "(pass L= / use a FiniteMPS), not on an InfiniteMPS")
+    return psi.engine.correlator(kind, connected=connected)
+
+
+def structure_factor(psi, kind, q, connected=True):
+    """S(q) = (1 / L) sum_ij exp(i q (i - j)) C_ij of correlation_function(psi, kind); q scalar or array (radians per site).
+    connected applies to the kinds that have a connected form ("nn", "szsz")."""
+    Cm = correlation_function(psi, kind, connected=connected and kind in ("nn", "szsz"))
+    L = Cm.shape[0]
+    qs = np.atleast_1d(np.asarray(q, dtype=float))
+    ph = np.exp(1j * qs[:, None] * np.arange(L)[None, :])                      # [q, i]
+    S = np.einsum("qi,ij,qj->q", ph, Cm, ph.conj()) / L
+    return S if np.ndim(q) else S[0]
+
+
+def momentum_distribution(psi, q):
+    """n(q) per spin: the "hop" structure factor halved (sum over q on the open-chain grid is not normalised: an open chain
+    has no momentum eigenstates, this is the Fourier transform of the one-particle density matrix)"""
+    return np.real(structure_factor(psi, "hop", q, connected=False)) / 2.0
+
+
 def TruncState(simul: Simulation, trunc_dim: int, trunc_scheme: int = 0, L: int | None = None, polish: str = "twosite", **kw):
     """truncated approximation of the ground state at bond dimension `trunc_dim` (TensorKit dim units), src:1351-1367.
     trunc_scheme 1 = SvdCut (truncate by SVD only); 0 = VUMPSSvdCut (truncate, then re-optimise variationally at

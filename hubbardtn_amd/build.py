@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("htn_abi.hip", "htn_gemm.hip", "htn_krylov.hip", "htn_svd.hip", "htn_qr.hip",
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("htn_abi.hip", "htn_gemm.hip", "htn_krylov.hip", "htn_svd.hip", "htn_qr.hip", "htn_measure.hip",
                                                 "htn_backend_hip.hip", "htn_plan.cpp", "htn_engine.cpp")]
 LIB = os.path.join(HERE, "csrc", "libhubbardtn_hip.so")
 INC = os.path.join(ROOT, "include")

@@ -74,6 +74,8 @@ struct HipBackend : htn::Backend {
     size_t pooled = 0;
     void* lan_scratch = nullptr;
     int64_t lan_scratch_elems = 0;
+    void* trd_scratch = nullptr;                  // partial sums of block_trdots
+    int64_t trd_scratch_elems = 0;
     void* comm = nullptr;
     char* stage = nullptr;                        // pinned host staging ring of upload()
     size_t stage_cap = (size_t)32 << 20, stage_pos = 0;
@@ -90,6 +92,7 @@ struct HipBackend : htn::Backend {
         for (auto& kv : free_list) (void)hipFree(kv.second);
         for (auto& kv : live) (void)hipFree(kv.first);
         if (lan_scratch) (void)hipFree(lan_scratch);
+        if (trd_scratch) (void)hipFree(trd_scratch);
         if (stage) (void)hipHostFree(stage);
         if (land) (void)hipHostFree(land);
         if (own_stream && st) (void)hipStreamDestroy(st);
@@ -293,6 +296,19 @@ struct HipBackend : htn::Backend {
     }
     int qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks) override {
         return htn_qr_blocks_z(A, R, desc_dev, desc_host, n_blocks, st);
+    }
+    int block_trdots(const void* A, const void* B, const htn_trdot_item* items_dev, const htn_trdot_item* items_host, int n_items,
+                     void* out, int n_out) override {
+        (void)items_host;
+        const int64_t need = htn_trdots_scratch_elems(n_items);
+        if (need > trd_scratch_elems) {              // (hipFree waits for the launches that still read the old block)
+            if (trd_scratch) HIP_TRY(hipFree(trd_scratch));
+            trd_scratch = nullptr, trd_scratch_elems = 0;
+            HIP_TRY(hipMalloc(&trd_scratch, sizeof(double2) * 2 * need));
+            trd_scratch_elems = 2 * need;
+            if (htn_debug_poison()) HIP_TRY(hipMemsetAsync(trd_scratch, 0xFF, sizeof(double2) * trd_scratch_elems, st));
+        }
+        return htn_block_trdots_z(A, B, items_dev, n_items, out, n_out, trd_scratch, st);
     }
     int batched_copy(void* dst, const void* src, const int32_t* idx, const double* scl, const htn_copy_item* items, int n_items,
                      double gscale) override {

@@ -341,6 +341,11 @@ struct Backend {
     // (htn_engine.cpp): download, Householder reflections on the host, upload -- what the CPU baseline library runs; the HIP
     // backend overrides it with the kernel.
     virtual int qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks);
+    // out[o] = sum of w * sum_{r,c} A[r, c] B[c, r] over the items of result o (htn_block_trdots_z in the header); every one of the
+    // n_out results is written.  Default (htn_engine.cpp): download the ranges the items touch, sum on the host in list order,
+    // upload -- what the CPU baseline library runs; the HIP backend overrides it with the kernel.
+    virtual int block_trdots(const void* A, const void* B, const htn_trdot_item* items_dev, const htn_trdot_item* items_host,
+                             int n_items, void* out, int n_out);
     virtual int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host,
                            int n_blocks, int max_m, int max_sweeps, double tol, int32_t* info_dev,
                            const htn_svd_opts* opts) = 0;

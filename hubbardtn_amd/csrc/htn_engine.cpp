@@ -288,6 +288,38 @@ int Backend::qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn
     return sync();
 }
 
+int Backend::block_trdots(const void* A, const void* B, const htn_trdot_item* items_dev, const htn_trdot_item* items, int n_items,
+                          void* out, int n_out) {
+    (void)items_dev;
+    if (n_out <= 0) return 0;
+    if (n_items > 0 && !items) return set_error("block_trdots: the host copy of the items is required");
+    int64_t a0 = INT64_MAX, a1 = 0, b0 = INT64_MAX, b1 = 0;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_trdot_item& it = items[q];
+        if (it.rows <= 0 || it.cols <= 0) continue;
+        a0 = std::min(a0, it.a_off), a1 = std::max(a1, it.a_off + (int64_t)(it.cols - 1) * it.lda + it.rows);
+        b0 = std::min(b0, it.b_off), b1 = std::max(b1, it.b_off + (int64_t)(it.rows - 1) * it.ldb + it.cols);
+    }
+    std::vector<cplx> ha((size_t)std::max<int64_t>(a1 - a0, 0)), hb((size_t)std::max<int64_t>(b1 - b0, 0)), res((size_t)n_out, cplx(0.0, 0.0));
+    if (!ha.empty() && download(ha.data(), (const cplx*)A + a0, sizeof(cplx) * ha.size())) return 1;
+    if (!hb.empty() && download(hb.data(), (const cplx*)B + b0, sizeof(cplx) * hb.size())) return 1;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_trdot_item& it = items[q];
+        if (it.out < 0 || it.out >= n_out) return set_error("block_trdots: item %d adds to result %d of %d", q, it.out, n_out);
+        if (it.rows <= 0 || it.cols <= 0) continue;
+        const cplx *a = ha.data() + (it.a_off - a0), *b = hb.data() + (it.b_off - b0);
+        double sr = 0.0, si = 0.0;                       // A[r, c] * B[c, r], no conjugation
+        for (int64_t c = 0; c < it.cols; ++c)
+            for (int64_t r = 0; r < it.rows; ++r) {
+                const cplx x = a[r + c * it.lda], y = b[c + r * it.ldb];
+                sr += x.real() * y.real() - x.imag() * y.imag();
+                si += x.real() * y.imag() + x.imag() * y.real();
+            }
+        res[(size_t)it.out] += cplx(it.w_re * sr - it.w_im * si, it.w_re * si + it.w_im * sr);
+    }
+    return upload(out, res.data(), sizeof(cplx) * res.size());
+}
+
 // Handles are reference counted: an htn_mps keeps its context and its MPO alive, so destroying the handles in any order
 // (garbage-collected host languages do exactly that) is safe; the last release frees the object.
 struct htn_ctx {
@@ -421,6 +453,10 @@ struct Gauge1C {                   // compiled gauge move of a one-site update: 
     DBufP desc_dev;
     int64_t rsize = 0;
     DevTasks absorb;
+};
+struct MeetC {                     // the items that pair the left and the right half of a correlator on one bond (htn_block_trdots_z)
+    std::vector<htn_trdot_item> items;
+    DBufP items_dev;
 };
 struct OrthState {                 // one attached state phi: overlap environments <psi|phi> per bond, carried along the sweep
     htn_mps* phi = nullptr;
@@ -597,6 +633,8 @@ struct htn_mps {
     int relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst);
     int update_site(int i, int direction, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
     int sweep1(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
+    // two-point correlation functions (htn_mps_correlator)
+    int correlator(const htn_corr_channel& ch, cplx* out_host, double* norm_host);
 };
 
 // One step of the H environment across site i.  side 'L': GL on bond i+1 from GL on bond i and the left-layout tensor of
@@ -1257,6 +1295,181 @@ int htn_mps::sweep1(const htn_sweep_opts& o, htn_bond_stats* st, double* E) {
     for (int i = L - 1; i >= 1; --i, ++k)
         if (update_site(i, -1, true, o, st ? st + k : nullptr)) return 1;
     if (E) *E = energy;
+    return 0;
+}
+
+// =====================================================================================================================
+// Two-point correlation functions C(i, j) = <close_j . pass ... pass . open_i> of one channel for all i <= j, the state read only
+// (htn_mps_correlator).  Both halves are environments of small probe MPO sites, planned by plan_left_env /
+// plan_right_env like the Hamiltonian's.  Those planners keep one level implicit (the left 'start', the right 'final': the
+// identity of a canonical state); the norm environments of a state in ANY gauge are not the identity, so the probes put an
+// unused level into that place and carry the norm level explicitly:
+//   left probe, every site      left [-, norm]   right [-, norm, open, done]      (norm -> norm, id) (norm -> open, open)
+//                                                                                 (norm -> done, onsite)
+//   right probe, site j         right [norm, open_{j+1} .. open_{L-1}, -]   left [norm, open_j, open_{j+1} .. open_{L-1}, -]
+//                                                                                 (norm <- norm, id) (open_j <- norm, close)
+//                                                                                 (open_j' <- open_j', pass)
+// The left pass keeps the output of every site (norm level first: the buffer is the next site's input as it stands); the right
+// pass keeps the current bond only and meets the left half of bond b = i + 1 in one block_trdots launch:
+//   C(i, j) = sum_{bra, ket} (2S_bra + 1) / (2S_ket + 1) tr(Lopen_i[bra, ket] Ropen_j[ket, bra])
+// -- the factor H_eff's apply closes a right environment with (coef_apply), independent of the level's spin and of the gauge:
+// the stored tensors of a path carry sqrt(2J + 1) in all (ovl_step's note) --, C(i, i) = <Lclosed_i, Rnorm>, <psi|psi> = <rho, Rnorm>.
+// Results of bond b go to row i of a device table shifted by one element: the norm lands in the unused slot (i, i - 1).
+// =====================================================================================================================
+int htn_mps::correlator(const htn_corr_channel& ch, cplx* out_host, double* norm_host) {
+    const Sym& sym = mpo->sym;
+    const char* who = "htn_mps_correlator";
+    if (ctx->world > 1 || ctx->shard || ctx->exch || be->has_comm())
+        return set_error("%s: not available on a context with a communicator or an exchange hook", who);
+    if (ch.open.dN + ch.close.dN != 0 || (sym.su2() ? ch.open.k != ch.close.k : ch.open.k + ch.close.k != 0))
+        return set_error("%s: the charges of open (dN %d, k %d) and close (dN %d, k %d) do not add up to zero", who, ch.open.dN, ch.open.k,
+                         ch.close.dN, ch.close.k);
+    if (ch.pass.dN != 0 || ch.pass.k != 0) return set_error("%s: the pass operator carries a charge (dN %d, k %d)", who, ch.pass.dN, ch.pass.k);
+    if (ch.has_onsite && (ch.onsite.dN != 0 || ch.onsite.k != 0))
+        return set_error("%s: the onsite operator carries a charge (dN %d, k %d)", who, ch.onsite.dN, ch.onsite.k);
+    if (Llay[0]->size != 0 || Rlay[L]->size != 0 || bonds[0]->multiplets() != 1 || bonds[L]->multiplets() != 1)
+        return set_error("%s: needs a finite chain with open ends (end bonds of one sector, dimension 1)", who);
+
+    // probe operators: 0 id, 1 open, 2 pass, 3 close, 4 onsite
+    Mpo pm;
+    pm.sym = sym;
+    auto add_op = [&](const htn_site_op& o) {
+        SiteOp r;
+        r.k = o.k, r.dN = o.dN;
+        for (int a = 0; a < HTN_MAX_SITE; ++a)
+            for (int b = 0; b < HTN_MAX_SITE; ++b) r.red[a][b] = o.red[a * HTN_MAX_SITE + b];
+        pm.ops.push_back(r);
+    };
+    htn_site_op ident;
+    memset(&ident, 0, sizeof(ident));
+    for (int s = 0; s < sym.n_site; ++s) ident.red[s * HTN_MAX_SITE + s] = 1.0;
+    add_op(ident), add_op(ch.open), add_op(ch.pass), add_op(ch.close), add_op(ch.onsite);
+    const bool onsite = ch.has_onsite != 0;
+    const Lvl scalar{0, 0}, open{ch.open.dN, ch.open.k};
+    const std::string tag((const char*)&ch, sizeof(ch));          // the probe's name in the plan cache: its operator tables
+    auto bkey = [&](int i) { return bonds[i]->key + "|" + bonds[i + 1]->key; };
+
+    // ---- left pass ----
+    MpoSite WL;
+    WL.left = {scalar, scalar};
+    WL.right = {scalar, scalar, open};
+    WL.entries = {{1, 1, 0, cplx(1.0)}, {1, 2, 1, cplx(1.0)}};
+    if (onsite) {
+        WL.right.push_back(scalar);
+        WL.entries.push_back({1, 3, 4, cplx(1.0)});
+    }
+    std::vector<EnvLayoutP> Hlay(L + 1);
+    std::vector<DView> Hbuf(L + 1);
+    Hbuf[0] = zalloc(1, false);
+    const cplx one(1.0, 0.0);
+    if (!Hbuf[0].base || be->upload(Hbuf[0].ptr(), &one, sizeof(one))) return set_error("%s: device allocation failed", who);
+    for (int i = 0; i < L; ++i) {
+        const SiteLayoutP lay = site_layout('L', bonds[i], bonds[i + 1]);
+        DView relaid;
+        const cplx* site = site_buf[i].ptr();
+        if (site_lay[i]->kind != 'L') {
+            relaid = zalloc(lay->size, false);
+            if (!relaid.base) return set_error("%s: device allocation failed", who);
+            if (relay(*site_lay[i], site, *lay, relaid.ptr())) return 1;
+            site = relaid.ptr();
+        }
+        auto c = cached<EnvC>("corrL" + tag + bkey(i), [&]() -> std::shared_ptr<EnvC> {
+            auto e = std::make_shared<EnvC>();
+            e->lay = build_env_layout(sym, 'L', bonds[i + 1], WL.right);
+            EnvPlan p;
+            plan_left_env(pm, *build_env_layout(sym, 'L', bonds[i], WL.left), *lay, WL, *e->lay, p);
+            return compile2(e, p);
+        });
+        if (!c) return 1;
+        DView z = zalloc(c->zsize, false), o = zalloc(c->lay->size, false);
+        if (!z.base || !o.base) return set_error("%s: device allocation failed", who);
+        if (gemm(c->d1, {{BUF_L, Hbuf[i].ptr()}, {BUF_S1, site}, {BUF_Z, z.ptr()}})) return 1;
+        if (gemm(c->d2, {{BUF_S1, site}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
+        Hlay[i + 1] = c->lay;
+        Hbuf[i + 1] = o;                            // kept until the right pass has met it: O(L chi^2) in all
+    }
+
+    // ---- right pass, meeting the left half on every bond ----
+    DView table = zalloc((int64_t)L * L + 1, true);
+    if (!table.base) return set_error("%s: device allocation failed", who);
+    std::vector<Lvl> rlev = {scalar, scalar};                      // levels of the right half on bond b: [norm, open_b .., -]
+    EnvLayoutP Rl = build_env_layout(sym, 'R', bonds[L], rlev);
+    DView Rb = zalloc(1, false);
+    if (!Rb.base || be->upload(Rb.ptr(), &one, sizeof(one))) return set_error("%s: device allocation failed", who);
+    for (int b = L; b >= 1; --b) {
+        const int i = b - 1, K = L - b + 1;                        // K levels: norm + one per closing site j >= b
+        if (b < L) {                                               // the right half crosses site b: bond b + 1 -> bond b
+            const SiteLayoutP lay = site_layout('R', bonds[b], bonds[b + 1]);
+            DView relaid;
+            const cplx* site = site_buf[b].ptr();
+            if (site_lay[b]->kind != 'R') {
+                relaid = zalloc(lay->size, false);
+                if (!relaid.base) return set_error("%s: device allocation failed", who);
+                if (relay(*site_lay[b], site, *lay, relaid.ptr())) return 1;
+                site = relaid.ptr();
+            }
+            MpoSite WR;
+            WR.right = rlev;
+            rlev.insert(rlev.begin() + 1, open);
+            WR.left = rlev;
+            WR.entries = {{0, 0, 0, cplx(1.0)}, {1, 0, 3, cplx(1.0)}};
+            for (int w = 1; w + 1 < (int)WR.right.size(); ++w) WR.entries.push_back({w + 1, w, 2, cplx(1.0)});
+            auto c = cached<EnvC>("corrR" + tag + ikey("K", K) + bkey(b), [&]() -> std::shared_ptr<EnvC> {
+                auto e = std::make_shared<EnvC>();
+                e->lay = build_env_layout(sym, 'R', bonds[b], WR.left);
+                EnvPlan p;
+                plan_right_env(pm, *Rl, *lay, WR, *e->lay, p);
+                return compile2(e, p);
+            });
+            if (!c) return 1;
+            DView z = zalloc(c->zsize, false), o = zalloc(c->lay->size, false);
+            if (!z.base || !o.base) return set_error("%s: device allocation failed", who);
+            if (gemm(c->d1, {{BUF_R, Rb.ptr()}, {BUF_S1, site}, {BUF_Z, z.ptr()}})) return 1;
+            if (gemm(c->d2, {{BUF_S1, site}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
+            Rl = c->lay;
+            Rb = o;
+        }
+        // results of this bond: 0 = <psi|psi>, 1 = C(i, i), 1 + (j - i) = C(i, j)
+        const EnvLayout& Ll = *Hlay[b];
+        auto m = cached<MeetC>("corrM" + tag + ikey("K", K) + bonds[b]->key, [&]() -> std::shared_ptr<MeetC> {
+            auto mc = std::make_shared<MeetC>();
+            auto pair = [&](int wl, int wr, int out) {
+                for (size_t q = 0; q < Ll.blocks.size(); ++q) {
+                    const Key& k = Ll.bkeys[q];
+                    if (k[2] != wl) continue;
+                    const Sec bra{k[0], k[1]}, ket{k[3], k[4]};
+                    const int rq = Rl->block(ket, wr, bra);
+                    if (rq < 0) continue;
+                    const auto &lb = Ll.blocks[q], &rb = Rl->blocks[rq];
+                    htn_trdot_item it;
+                    memset(&it, 0, sizeof(it));
+                    it.a_off = lb.off, it.b_off = rb.off;
+                    it.rows = lb.m, it.cols = lb.n, it.lda = lb.m, it.ldb = rb.m;
+                    it.out = out;
+                    it.w_re = (double)sym.qdim(bra) / (double)sym.qdim(ket);
+                    mc->items.push_back(it);
+                }
+            };
+            pair(1, 0, 0);
+            if (onsite) pair(3, 0, 1);
+            for (int j = b; j < L; ++j) pair(2, 1 + (j - b), 1 + (j - i));
+            if (!(mc->items_dev = upload_vec(be, mc->items))) return nullptr;
+            return mc;
+        });
+        if (!m) return 1;
+        if (be->block_trdots(Hbuf[b].ptr(), Rb.ptr(), (const htn_trdot_item*)m->items_dev->p, m->items.data(), (int)m->items.size(),
+                             table.ptr() + ((int64_t)i * L + i), K + 1))
+            return 1;
+        Hbuf[b] = DView();
+    }
+    std::vector<cplx> t((size_t)L * L + 1);
+    if (be->download(t.data(), table.ptr(), sizeof(cplx) * t.size())) return 1;
+    for (int i = 0; i < L; ++i) {
+        const cplx nrm = t[(size_t)i * L + i];
+        if (!(std::abs(nrm) > 0.0)) return set_error("%s: <psi|psi> = %g on bond %d", who, nrm.real(), i + 1);
+        if (i == 0 && norm_host) *norm_host = nrm.real();
+        for (int j = 0; j < L; ++j) out_host[(size_t)i * L + j] = j > i || (j == i && onsite) ? t[1 + (size_t)i * L + j] / nrm : cplx(0.0, 0.0);
+    }
     return 0;
 }
 
@@ -2135,6 +2348,12 @@ int htn_mps_overlap(htn_mps* a, const htn_mps* b, double* out_host) {
     out_host[0] = v.real();
     out_host[1] = v.imag();
     return 0;
+}
+
+int htn_mps_correlator(htn_mps* mps, const htn_corr_channel* ch, void* out_host, double* norm_host) {
+    if (!mps || !ch || !out_host) return set_error("htn_mps_correlator: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->correlator(*ch, (cplx*)out_host, norm_host);
 }
 
 int64_t htn_mps_theta_size(htn_mps* mps, int32_t i) {

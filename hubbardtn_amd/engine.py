@@ -529,6 +529,72 @@ class DMRG2:
         self.energy = E
         return E
 
+    # ---- two-point correlation functions (htn_mps_correlator) ----------------------------------------
+    def _site_op(self, name) -> abi.SiteOp:
+        k, dN, red = self.sym.site_ops[name]
+        op = abi.SiteOp()
+        op.k, op.dN = int(k), int(dN)
+        r = np.zeros((abi.MAX_SITE, abi.MAX_SITE))
+        r[:red.shape[0], :red.shape[1]] = red
+        op.red[:] = list(r.reshape(-1))
+        return op
+
+    def correlator_channel(self, op_open, op_pass, op_close, op_onsite=None):
+        """one channel, by site-operator names of the symmetry: C[i, j] = <close_j pass.. open_i> for i < j (coefficient 1 of the
+        Hamiltonian term with these operators), C[i, i] = <onsite_i> if given, zeros below the diagonal; already divided by
+        <psi|psi>.  One pass on the device, the state is only read (any centre position).  -> (C, <psi|psi>)"""
+        ch = abi.CorrChannel()
+        ch.open, ch.pass_, ch.close = self._site_op(op_open), self._site_op(op_pass), self._site_op(op_close)
+        if op_onsite is not None:
+            ch.onsite, ch.has_onsite = self._site_op(op_onsite), 1
+        out = np.zeros((self.L, self.L), dtype=np.complex128)
+        nrm = C.c_double(0.0)
+        self._check(self.lib.htn_mps_correlator(self.handle, C.byref(ch), out.ctypes.data, C.byref(nrm)), "htn_mps_correlator")
+        return out, nrm.value
+
+    def correlator(self, kind, connected=False):
+        """Hermitian ndarray[L, L] of two-point functions of the state as stored: kind "hop": sum_s <c+_is c_js>, "nn": <n_i n_j>,
+        "ss": <S_i . S_j>, "pair": <D+_i D_j> (D = c_dn c_up); in the spinful U(1) x U(1) mode also the single channels "hop_up",
+        "hop_dn", "szsz", "s+-" (<S+_i S-_j>), "s-+".  Operators, Jordan-Wigner strings and factors are the symmetry's term
+        channels (models.TERM_CHANNELS*), the tables the Hamiltonian builder uses; the diagonal holds the one-site products n, n^2,
+        S^2 = 3/4 (n - 2 docc), docc.  Channels that come as a Hermitian-conjugate pair ("hop+" / "hop-") fill the upper / the
+        lower triangle, otherwise the lower triangle is the conjugate of the upper.  connected=True ("nn", "szsz") subtracts
+        <n_i><n_j> (<sz_i><sz_j>)."""
+        from .models import CORR_ONSITE, CORR_ONSITE_U1
+        chans = self.sym.channels
+        onsite = (CORR_ONSITE if self.sym.su2 else CORR_ONSITE_U1).get(kind)
+        if kind in ("hop", "nn", "ss", "pair") and kind in chans:
+            use = [(c, c[5]) for c in chans[kind]]
+        elif not self.sym.su2 and kind in ("hop_up", "hop_dn"):
+            use = [(c, c[5]) for c in chans["hop"] if c[0].startswith(kind)]
+        elif not self.sym.su2 and kind in ("szsz", "s+-", "s-+"):
+            use = [(c, 1.0) for c in chans["ss"] if c[0] == kind]
+        else:
+            raise ValueError(f"correlator kind '{kind}' is not available in the {self.sym.name} mode")
+        if connected and kind not in ("nn", "szsz"):
+            raise ValueError("connected=True is defined for 'nn' and 'szsz'")
+        names = {c[0] for c, _ in use}
+        upper = np.zeros((self.L, self.L), dtype=np.complex128)
+        lower = None
+        diag = None
+        for (name, _q, op_open, op_pass, op_close, _f), fac in use:
+            partner = name.endswith("-") and name[:-1] + "+" in names       # the h.c. of an upper channel: <.._j .._i>, j > i
+            first = diag is None and not partner
+            M, _ = self.correlator_channel(op_open, op_pass, op_close, onsite if first else None)
+            if first:
+                diag = np.diag(M).copy()
+                M = M - np.diag(diag)
+            if partner:
+                lower = fac * M if lower is None else lower + fac * M
+            else:
+                upper += fac * M
+        Cm = upper + (upper.conj().T if lower is None else lower.T) + np.diag(diag)
+        if connected:
+            one = "n" if kind == "nn" else "sz"
+            m = np.real(np.diag(self.correlator_channel(one, "id", one, one)[0]))
+            Cm = Cm - np.outer(m, m)
+        return Cm
+
     def site_energies(self):
         """genuine <psi|H|psi> of the state as stored, split per site: e_i = energy of all Hamiltonian terms that END
         on site i (on-site terms of i, and every two-site term whose right-most site is i); sum(e) = <psi|H|psi>.

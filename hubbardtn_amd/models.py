@@ -54,6 +54,12 @@ SITE_OPS = {
     "Fc_d": (1, -1, _mat({(1, 2): -1})),
 }
 
+# one-site products of the two-point correlators (engine.DMRG2.correlator): the i == j entry of each kind, by name in the
+# table above -- hop: sum_s c+_s c_s = n; nn: n^2; ss: S.S = 3/4 (n - 2 docc); pair: D+ D = docc
+SITE_OPS["n2"] = (0, 0, _mat({(1, 1): 1, (2, 2): 4}))
+SITE_OPS["S2"] = (0, 0, _mat({(1, 1): 0.75}))
+CORR_ONSITE = {"hop": "n", "nn": "n2", "ss": "S2", "pair": "docc"}
+
 # two-site term kinds -> channels (name, (dN, k) carried by the virtual level, opening op, pass-through op,
 # closing op, closing factor).  Factors are fixed by the dense checks of tests/test_host_cpu.py:
 #   hop  : coef * sum_s (c+_{i s} c_{j s} + h.c.)      nn  : coef * n_i n_j
@@ -162,6 +168,14 @@ SITE_OPS_U1 = {
     "cdagF_dn_d": (-1, +1, _N_UP @ _A_DN.T @ _F4), "c_dn_d": (+1, -1, _N_UP @ _A_DN),
     "Fc_dn_d": (+1, -1, _F4 @ _N_UP @ _A_DN), "cdag_dn_d": (-1, +1, _N_UP @ _A_DN.T),
 }
+# one-site products of the two-point correlators, spinful mode (kinds and single channels of engine.DMRG2.correlator)
+SITE_OPS_U1.update({
+    "n2": (0, 0, np.diag([0.0, 1.0, 1.0, 4.0])), "S2": (0, 0, np.diag([0.0, 0.75, 0.75, 0.0])),
+    "n_up": (0, 0, _N_UP.copy()), "n_dn": (0, 0, _N_DN.copy()), "sz2": (0, 0, np.diag([0.0, 0.25, 0.25, 0.0])),
+    "spsm": (0, 0, np.diag([0.0, 1.0, 0.0, 0.0])), "smsp": (0, 0, np.diag([0.0, 0.0, 1.0, 0.0])),
+})
+CORR_ONSITE_U1 = {"hop": "n", "nn": "n2", "ss": "S2", "pair": "docc", "hop_up": "n_up", "hop_dn": "n_dn", "szsz": "sz2",
+                  "s+-": "spsm", "s-+": "smsp"}
 # c+_{i s} c_{j s} = (a+_s F)_i F.. (a_s)_j ;  c+_{j s} c_{i s} = (F a_s)_i F.. (a+_s)_j   (i < j): unit factors
 TERM_CHANNELS_U1 = {
     "hop": (("hop_up+", (+1, +1), "cdagF_up", "F", "c_up", 1.0), ("hop_up-", (-1, -1), "Fc_up", "F", "cdag_up", 1.0),

@@ -263,6 +263,31 @@ int htn_qr_blocks_z(void* A, void* Rbuf, const htn_qr_block* desc, const htn_qr_
                     void* stream);
 
 
+/* Batched block trace-dots: the pairing of a left environment (blocks stored [n_bra x n_ket]) with right environments
+ * (blocks stored [n_ket x n_bra]) that closes a two-point correlation function on a bond (htn_mps_correlator).  The sum
+ * runs over A[r, c] * B[c, r]: one operand is read transposed and nothing is conjugated, which htn_dots_z cannot express.
+ *   out[o] = sum over items with item.out == o, in list order, of
+ *            w * sum_{r,c} A[a_off + r + c*lda] * B[b_off + c + r*ldb];       results with no item are written as 0
+ * Two stages, no floating-point atomics: every item is cut into 32 x 32 tiles, the tiles are dealt to HTN_TRDOT_SLOTS
+ * work units per item (one workgroup each, so a large block does not serialise the launch; the B tile goes through LDS so
+ * that both operands are read along their contiguous direction), each unit adds its tiles in a fixed order; the second
+ * stage adds the units of an item in slot order and the items of a result in list order.  Repeated calls are bit-identical.
+ * Any sizes: blocks of one row or one column and blocks that are no multiple of the tile are fine; n_items = 0 writes zeros.
+ * items: device array; scratch: htn_trdots_scratch_elems(n_items) complex128. */
+#define HTN_TRDOT_SLOTS 16
+typedef struct {
+    int64_t a_off, b_off;       /* element offsets into A and B                                       */
+    int32_t rows, cols;         /* A block: rows x cols, column-major, lda; B block: cols x rows, ldb */
+    int32_t lda, ldb;
+    int32_t out;                /* index of the result this item adds to                              */
+    int32_t pad[3];             /* (pads the record to 64 bytes, the size of the other task records)  */
+    double w_re, w_im;          /* weight                                                             */
+} htn_trdot_item;               /* 64 bytes */
+int64_t htn_trdots_scratch_elems(int32_t n_items);
+int htn_block_trdots_z(const void* A, const void* B, const htn_trdot_item* items, int32_t n_items,
+                       void* out, int32_t n_out, void* scratch, void* stream);
+
+
 /* =====================================================================================================
  * Bond-update / sweep level (ABI 2): what sits behind
  *     find_groundstate(psi0, H, IDMRG2(; trscheme, tol))          src/HubbardFunctions.jl:1010
@@ -448,6 +473,27 @@ int htn_mps_set_orthogonal(htn_mps* mps, const htn_mps* const* others_host, int3
 int32_t htn_mps_orthogonal_count(const htn_mps* mps, int32_t* dropped_host);
 /* out_host[0..1] = <a|b> (re, im) by a transfer pass on the device; 0 for states in different total sectors */
 int htn_mps_overlap(htn_mps* a, const htn_mps* b, double* out_host);
+
+/* Two-point correlation functions of a finite chain, measured on the device without touching the state.  One call gives one
+ * CHANNEL for all pairs i <= j: `open` acts on site i, `pass` on the sites strictly between (the Jordan-Wigner string of a
+ * fermionic channel, else the identity), `close` on site j; `onsite` (has_onsite) is the one-site product for i == j.  The
+ * operators are reduced site operators in the conventions of htn_site_op, exactly what an MPO channel of htn_mpo_create
+ * carries: <close . pass ... pass . open> is what the Hamiltonian term with these three operators and coefficient 1 measures.
+ * Method: a left pass carries the norm environment and forms, per site i, the environment with `open` (and `onsite`) applied
+ * on i; a right pass carries the right norm environment plus one open level per closing site j (all levels of a site in the
+ * two grouped-GEMM launches of one plan); on every bond the halves meet in ONE htn_block_trdots_z launch, block weight
+ * (2S_bra + 1) / (2S_ket + 1) (1 in the abelian kind).  Nothing synchronises inside the pass; the table is downloaded once.
+ * The norm environments are carried explicitly, so the centre may sit anywhere and the state is not re-gauged.
+ * out_host: L*L complex128, row-major, entry [i*L + j] for i <= j (i == j only with has_onsite), everything else 0;
+ * already divided by <psi|psi>, which is also returned in norm_host (may be NULL).  The state is not modified.
+ * Errors: `open` and `close` charges that do not add up to zero, a `pass` (or `onsite`) operator that carries a charge, a
+ * chain with boundary environments (an iDMRG window), a context with a communicator or an exchange hook (not verified). */
+typedef struct {
+    htn_site_op open, pass, close;  /* on site i, on the sites between, on site j  (i < j)               */
+    htn_site_op onsite;             /* the one-site product for i == j; used only if has_onsite          */
+    int32_t has_onsite, pad;
+} htn_corr_channel;                 /* 552 bytes */
+int htn_mps_correlator(htn_mps* mps, const htn_corr_channel* ch, void* out_host, double* norm_host);
 
 /* y = H_eff(bond i, i+1) x on host vectors in the library's theta layout (size htn_mps_theta_size); tests and
  * Hermiticity checks.  x and y are complex128 host arrays. */
