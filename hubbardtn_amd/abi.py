@@ -123,7 +123,7 @@ assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(Idmr
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
            "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z",
-           "htn_trdots_scratch_elems", "htn_block_trdots_z"]
+           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z"]
 # entry points shared by libhubbardtn_hip.so and the CPU baseline library (oracle/cpu_backend)
 ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_ctx_set_timing", "htn_comm_unique_id",
                   "htn_ctx_set_comm", "htn_ctx_set_exchange", "htn_mpo_create", "htn_mpo_destroy", "htn_mps_create",
@@ -134,7 +134,8 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_idmrg_create", "htn_idmrg_destroy", "htn_idmrg_boundary", "htn_idmrg_step", "htn_idmrg_window",
                   "htn_mps_set_orthogonal", "htn_mps_orthogonal_count", "htn_mps_overlap",
                   "htn_site_update", "htn_dmrg1_sweep", "htn_mps_centre", "htn_mps_site_theta_size", "htn_heff1_apply",
-                  "htn_qr_blocks_z", "htn_mps_correlator"]
+                  "htn_qr_blocks_z", "htn_mps_correlator",
+                  "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo"]
 
 
 class GemmLaunch(C.Structure):
@@ -187,6 +188,7 @@ def load_library(path: str | None = None):
     lib.htn_trdots_scratch_elems.argtypes = [i32]
     lib.htn_trdots_scratch_elems.restype = i64
     lib.htn_block_trdots_z.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+    lib.htn_krylov_combine_z.argtypes = [vp, i64, i32, vp, i64, vp]
     declare_engine(lib)
     for name in EXPORTS + ENGINE_EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
@@ -258,6 +260,13 @@ def declare_engine(lib):
     lib.htn_heff1_apply.argtypes = [vp, i32, vp, vp]
     lib.htn_qr_blocks_z.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.htn_mps_correlator.argtypes = [vp, C.POINTER(CorrChannel), vp, C.POINTER(f64)]
+    lib.htn_krylov_expm_z.argtypes = [C.POINTER(GemmLaunch), i32, i32, i32, vp, i64, i32, f64, f64, f64, i32, vp, i32,
+                                      EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i32), C.POINTER(f64),
+                                      C.POINTER(f64), vp]
+    lib.htn_bond_evolve.argtypes = [vp, i32, i32, i32, f64, f64, C.POINTER(SweepOpts), vp]
+    lib.htn_site_evolve.argtypes = [vp, i32, f64, f64, C.POINTER(SweepOpts), vp]
+    lib.htn_tdvp2_sweep.argtypes = [vp, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
+    lib.htn_mps_set_mpo.argtypes = [vp, vp]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

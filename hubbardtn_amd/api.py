@@ -79,6 +79,16 @@ class IDMRG2:
 
 
 @dataclass
+class TDVP2:
+    """two-site TDVP selector (MPSKit.TDVP2 keyword names): trscheme truncates every bond step, tol is the tolerance of the
+    Krylov exponential, maxrestart the number of sub-steps a solve may take when krylovdim vectors do not reach it"""
+    trscheme: object = None
+    krylovdim: int = 30
+    tol: float = 1e-10
+    maxrestart: int = 8
+
+
+@dataclass
 class InfiniteHamiltonian:
     """the model of a translation-invariant chain; len() = sites per unit cell (length(H) in the reference)"""
     simul: Simulation
@@ -261,6 +271,65 @@ def find_groundstate(psi: FiniteMPS, H, alg: DMRG2, envs=None):
         if delta < alg.tol:
             break
     return psi, Environments(eng), delta
+
+
+def _tdvp_setup(psi, H, alg):
+    if isinstance(psi, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
+        raise NotImplementedError("time evolution of the infinite chain is not available: give a chain length L")
+    if not isinstance(alg, TDVP2):
+        raise TypeError("timestep / time_evolve take alg = TDVP2(...)")
+    eng = psi.engine
+    if isinstance(alg.trscheme, truncdim):
+        eng.chi_full, eng.cutoff = int(alg.trscheme.D), 0.0
+    elif isinstance(alg.trscheme, truncbelow):
+        eng.chi_full, eng.cutoff = None, float(alg.trscheme.eta)
+    elif alg.trscheme is None:
+        eng.chi_full, eng.cutoff = None, 0.0
+    else:
+        raise TypeError("trscheme must be truncdim(D) or truncbelow(eta)")
+    eng.krylovdim, eng.lanczos_tol, eng.maxrestart = int(alg.krylovdim), float(alg.tol), int(alg.maxrestart)
+    if H is not None and H is not eng.mpo and H is not eng.cmpo:
+        eng.set_mpo(H)          # the quench: another Hamiltonian under the same state
+    return eng
+
+
+def timestep(psi: FiniteMPS, H, dt, alg: TDVP2, envs=None):
+    """one two-site TDVP step psi <- exp(-i dt H) psi in place (MPSKit.timestep; dt complex, -i beta is imaginary time and the
+    state stays normalised).  H other than the state's current MPO replaces it first (engine.DMRG2.set_mpo).
+    -> (psi, envs)"""
+    eng = _tdvp_setup(psi, H, alg)
+    eng.tdvp_sweep(dt)
+    return psi, Environments(eng)
+
+
+def time_evolve(psi: FiniteMPS, H, times, alg: TDVP2, observe=None):
+    """evolve psi through the increasing list `times` (MPSKit.time_evolve; the state is at times[0] on entry), one TDVP step per
+    interval.  With observe: the list of observe(psi, t) for every t of `times`.  Without: a dict of arrays over the times --
+    "times", "energy" (<psi|H|psi>), "density_state" and "double_occupancy" ([len(times), L]), "loschmidt" (<psi(t0)|psi(t)>,
+    complex) and "trunc_weight" (discarded weight of the step that led to each time, 0 for the first)."""
+    eng = _tdvp_setup(psi, H, alg)
+    times = [complex(t) if isinstance(t, complex) else float(t) for t in times]
+    out = []
+    psi0 = None
+    if observe is None:
+        psi0 = eng.copy()       # the echo needs the initial state: one copy before the first step
+
+    def record(t, tw):
+        if observe is not None:
+            return observe(psi, t)
+        n, d = eng.site_occupations()
+        E, _ = eng.bond_energies()
+        return {"t": t, "energy": E, "n": n, "d": d, "echo": psi0.overlap(eng), "tw": tw}
+    out.append(record(times[0], 0.0))
+    for t0, t1 in zip(times[:-1], times[1:]):
+        k0 = len(eng.stats)
+        eng.tdvp_sweep(t1 - t0)
+        out.append(record(t1, float(sum(s.trunc_weight for s in eng.stats[k0:]))))
+    if observe is not None:
+        return out
+    return {"times": np.array(times), "energy": np.array([r["energy"] for r in out]),
+            "density_state": np.array([r["n"] for r in out]), "double_occupancy": np.array([r["d"] for r in out]),
+            "loschmidt": np.array([r["echo"] for r in out]), "trunc_weight": np.array([r["tw"] for r in out])}
 
 
 def compute_groundstate(simul: Simulation, L: int | None = None, tol: float = 1e-6, verbosity: int = 0,

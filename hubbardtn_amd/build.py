@@ -18,6 +18,7 @@ def needs_build() -> bool:
         return True
     t = os.path.getmtime(LIB)
     deps = SRCS + [os.path.join(HERE, "csrc", "htn_common.h"), os.path.join(HERE, "csrc", "htn_core.h"),
+                   os.path.join(HERE, "csrc", "htn_expm.h"),
                    os.path.join(INC, "hubbardtn_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -258,6 +258,17 @@ struct HipBackend : htn::Backend {
         *n_matvec = nmv;
         return rc;
     }
+    int krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim, double dt_re,
+                    double dt_im, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, double* growth,
+                    double* alpha0, int* n_matvec, double* err, double* matvec_ms) override {
+        if (krylovdim < 2 || krylovdim > 31) return htn::set_error("krylov_expm: krylovdim must be in 2..31");
+        if (ensure_lan_scratch(htn_lanczos_scratch_elems(krylovdim))) return 1;
+        int32_t nmv = 0;
+        const int rc = htn_krylov_expm_z(stages, n_stages, x_slot, y_slot, V, n, krylovdim, dt_re, dt_im, tol, max_restart, lan_scratch,
+                                         zero_y, exchange, user, growth, alpha0, &nmv, err, matvec_ms, st);
+        *n_matvec = nmv;
+        return rc;
+    }
     // Gram-Schmidt of the projector rows on the device (htn_dots_z / htn_axpys_z, two passes per row); the host sees two
     // squared norms per row and decides whether the row stays
     int orthonormalise_rows(void* Pv, int64_t n, int nvec, double drop_tol, int* kept) override {

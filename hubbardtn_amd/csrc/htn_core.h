@@ -334,6 +334,13 @@ struct Backend {
     virtual int lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n,
                              int krylovdim, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
                              const void* Q, int n_frozen, double* eig, int* n_matvec, double* residual, double* matvec_ms);
+    // x = exp(-i dt H) x0 on the device row V[0] (htn_krylov_expm_z in the header: outputs, stopping and sub-stepping rule).
+    // NOT pure: the default (htn_engine.cpp) is a plain host statement of the method -- vectors downloaded, H applied through
+    // grouped_gemm, full two-pass reorthogonalisation, the decisions of htn_expm::Expm -- which the CPU baseline library
+    // inherits; the HIP backend overrides it with htn_krylov_expm_z.
+    virtual int krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim,
+                            double dt_re, double dt_im, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
+                            double* growth, double* alpha0, int* n_matvec, double* err, double* matvec_ms);
     // Gram-Schmidt (two passes) of the nvec device rows P in place, in order; a row whose remainder falls below drop_tol x its
     // norm is dropped and the rows behind it move up.  -> *kept orthonormal rows.  Default: on the host.
     virtual int orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept);

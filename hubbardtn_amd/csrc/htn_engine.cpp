@@ -19,6 +19,7 @@
 #include <map>
 
 #include "htn_core.h"
+#include "htn_expm.h"
 
 namespace htn {
 Backend* make_backend(int backend, int device, void* stream);       // one per library (htn_backend_hip.hip / cpu)
@@ -167,6 +168,78 @@ int Backend::lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slo
     *eig = theta;
     *n_matvec = nmv;
     *residual = res;
+    if (matvec_ms) *matvec_ms = 0.0;
+    return 0;
+}
+
+// x = exp(-i dt H) x0, host statement (htn_core.h): the Lanczos basis with full two-pass reorthogonalisation on host copies of
+// the vectors, H through grouped_gemm, the stopping / sub-stepping decisions of htn_expm::Expm -- the ones the device driver takes
+int Backend::krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* Vv, int64_t n, int kd, double dt_re,
+                         double dt_im, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, double* growth,
+                         double* alpha0, int* n_matvec, double* err, double* matvec_ms) {
+    if (kd < 2 || kd > 31) return set_error("krylov_expm: krylovdim must be in 2..31");
+    if (!Vv || n <= 0) return set_error("krylov_expm: bad arguments");
+    cplx* Vd = (cplx*)Vv;
+    const size_t bytes = sizeof(cplx) * (size_t)n;
+    std::vector<cplx> B((size_t)(kd + 1) * n), x((size_t)n);
+    if (download(B.data(), Vd, bytes)) return 1;
+    auto matvec = [&](const cplx* v, cplx* w) -> int {        // through device rows kd (x) and kd + 1 (y) of the caller's V
+        cplx *xd = Vd + (int64_t)kd * n, *yd = Vd + (int64_t)(kd + 1) * n;
+        if (upload(xd, v, bytes)) return 1;
+        if (zero_y && zero(yd, bytes)) return 1;
+        for (int s = 0; s < n_stages; ++s) {
+            const void* bufs[HTN_MAX_BUFS];
+            for (int b = 0; b < HTN_MAX_BUFS; ++b) bufs[b] = stages[s].bufs[b];
+            bufs[x_slot] = xd;
+            bufs[y_slot] = yd;
+            if (stages[s].n_tiles > 0 && grouped_gemm(bufs, stages[s].tiles, stages[s].n_tiles, stages[s].segs)) return 1;
+        }
+        if (exchange && exchange(yd, n, user)) return set_error("krylov_expm: the exchange hook reported a failure");
+        return download(w, yd, bytes);
+    };
+    {
+        const double nn = hdot(B.data(), B.data(), n).real();
+        if (!(nn > 0.0)) return set_error("krylov_expm: the start vector is zero or not finite");
+        const double sc = 1.0 / sqrt(nn);
+        for (int64_t e = 0; e < n; ++e) B[(size_t)e] *= sc;
+    }
+    htn_expm::Expm ex;
+    ex.dt_re = dt_re, ex.dt_im = dt_im, ex.tol = tol;
+    int nmv = 0;
+    for (int restart = 0;; ++restart) {
+        ex.begin_cycle();
+        for (int j = 0; j < kd; ++j) {
+            cplx* w = B.data() + (int64_t)(j + 1) * n;
+            if (matvec(B.data() + (int64_t)j * n, w)) return 1;
+            ++nmv;
+            std::vector<const cplx*> rows;
+            for (int r = 0; r <= j; ++r) rows.push_back(B.data() + (int64_t)r * n);
+            const double alpha = hproject(rows, w, n, j);
+            const double beta = sqrt(hdot(w, w, n).real());
+            if (!(alpha == alpha) || !(beta == beta)) return set_error("krylov_expm: NaN in the tridiagonal coefficients");
+            bool bad = false;
+            const bool stop = ex.step(alpha, beta, kd, &bad);
+            if (bad) return set_error("krylov_expm: the QL iteration of the tridiagonal matrix did not converge");
+            if (stop) break;
+            const double inv = 1.0 / beta;
+            for (int64_t e = 0; e < n; ++e) w[e] *= inv;
+        }
+        if (!ex.converged && restart >= max_restart)
+            return set_error("krylov_expm: not converged after %d restart(s) of krylovdim %d: fraction %.3e of dt remains (estimate %.3e, tol %.3e)",
+                             std::max(max_restart, 0), kd, ex.remaining, ex.est, tol);
+        if (!ex.finish()) return set_error("krylov_expm: no fraction of the step down to 2^-60 meets the tolerance");
+        const int m = (int)ex.c.size();
+        std::fill(x.begin(), x.end(), cplx(0.0, 0.0));
+        for (int r = 0; r < m; ++r)
+            for (int64_t e = 0; e < n; ++e) x[(size_t)e] += ex.c[(size_t)r] * B[(size_t)r * n + e];
+        memcpy((void*)B.data(), x.data(), bytes);
+        if (ex.remaining == 0.0) break;
+    }
+    if (upload(Vd, B.data(), bytes) || sync()) return 1;
+    *growth = ex.growth;
+    *alpha0 = ex.alpha0;
+    *n_matvec = nmv;
+    *err = ex.err_total;
     if (matvec_ms) *matvec_ms = 0.0;
     return 0;
 }
@@ -468,6 +541,7 @@ struct Solve {                     // the eigenproblem of one update (compiled a
     int64_t n = 0;
     double E = 0.0, res = 0.0, mv_ms = 0.0;
     int nmv = 0;
+    double growth = 1.0;           // evolving updates: |x| / |x0| of the exponential
 };
 struct BondWork {                  // what flows between the steps of one two-site update (htn_mps::update_bond)
     ThetaLayoutP tl;
@@ -618,7 +692,7 @@ struct htn_mps {
     int apply_once(const ApplyC& ap, const DView& L, const DView& R, int64_t n, const void* x_host, void* y_host, bool exchange);
     int theta_into(int i, const ThetaLayout& tl, cplx* dst);
     // two-site update: update_bond runs these once each, in this order
-    int bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w);
+    int bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w, const cplx* evolve_dt = nullptr);
     std::shared_ptr<SvdC> make_svd(int i, const ThetaLayout& tl, bool right);
     int bond_svd(int i, bool right, const htn_sweep_opts& o, BondWork& w);
     int bond_truncate(int i, const htn_sweep_opts& o, BondWork& w);
@@ -627,8 +701,14 @@ struct htn_mps {
     void bond_spectrum(int i, const BondWork& w);
     void fill_stats(htn_bond_stats* st, int bond, int direction, const Solve& sol, int64_t env_elems, int jacobi_sweeps,
                     int64_t svd_flops, double trunc_weight, const StageClock& clk);
-    int update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
+    int update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st,
+                    const cplx* evolve_dt = nullptr, double* log_growth = nullptr);
     int sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
+    // time evolution (htn_bond_evolve / htn_site_evolve / htn_tdvp2_sweep / htn_mps_set_mpo)
+    int evolve_checks(const htn_sweep_opts& o, const char* who) const;
+    int evolve_site(int i, cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* log_growth);
+    int tdvp2_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* E, double* log_norm);
+    int set_mpo(htn_mpo* m);
     // one-site DMRG (htn_site_update / htn_dmrg1_sweep)
     int relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst);
     int update_site(int i, int direction, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st);
@@ -863,7 +943,7 @@ void htn_mps::fill_stats(htn_bond_stats* st, int bond, int direction, const Solv
 
 // ---- two-site update, step by step ----------------------------------------------------------------
 // solve: theta -> V[0], the compiled apply, the projector rows of attached states (optimising updates), Lanczos
-int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w) {
+int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w, const cplx* evolve_dt) {
     w.tl = theta_layout(bonds[i], bonds[i + 2]);
     const ThetaLayout& tl = *w.tl;
     Solve& s = w.sol;
@@ -895,7 +975,11 @@ int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageCloc
         if (be->orthonormalise_rows(w.Qb.ptr(), n, na, 1e-12, &n_frozen)) return 1;
         orth_dropped = na - n_frozen;
     }
-    if (n_frozen > 0) {
+    if (evolve_dt) {            // (evolving update: theta <- exp(-i dt H_eff) theta; E = <theta|H_eff|theta> before the step)
+        if (be->krylov_expm(stages, ns, BUF_X, BUF_Y, w.V.ptr(), n, kd, evolve_dt->real(), evolve_dt->imag(), o.lanczos_tol, o.maxrestart, 0,
+                            nullptr, ctx, &s.growth, &s.E, &s.nmv, &s.res, be->timing ? &s.mv_ms : nullptr))
+            return 1;
+    } else if (n_frozen > 0) {
         if (be->lanczos_orth(stages, ns, BUF_X, BUF_Y, w.V.ptr(), n, kd, o.lanczos_tol, o.maxrestart, shard ? 1 : 0,
                              shard ? exchange_tramp : nullptr, ctx, w.Qb.ptr(), n_frozen, &s.E, &s.nmv, &s.res,
                              be->timing ? &s.mv_ms : nullptr))
@@ -1143,11 +1227,13 @@ void htn_mps::bond_spectrum(int i, const BondWork& w) {
     spectra[i + 1] = std::move(spec);
 }
 
-int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st) {
+int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st,
+                         const cplx* evolve_dt, double* log_growth) {
     if (i < 0 || i + 1 >= L) return set_error("htn_bond_update: bond index %d out of range", i);
     StageClock clk(be, o.profile);
     BondWork w;
-    if (bond_solve(i, optimise, o, clk, w)) return 1;          // (laps clk.plan and clk.lanczos)
+    if (bond_solve(i, optimise, o, clk, w, evolve_dt)) return 1;          // (laps clk.plan and clk.lanczos)
+    if (log_growth) *log_growth += log(w.sol.growth);
     const double t_svd0 = clk.last;
     if (bond_svd(i, right, o, w)) return 1;
     if (bond_truncate(i, o, w)) return 1;
@@ -1295,6 +1381,122 @@ int htn_mps::sweep1(const htn_sweep_opts& o, htn_bond_stats* st, double* E) {
     for (int i = L - 1; i >= 1; --i, ++k)
         if (update_site(i, -1, true, o, st ? st + k : nullptr)) return 1;
     if (E) *E = energy;
+    return 0;
+}
+
+// =====================================================================================================================
+// Time evolution: two-site TDVP (htn_bond_evolve / htn_site_evolve / htn_tdvp2_sweep).  A bond step is
+// update_bond with Backend::krylov_expm in the place of the eigen-solve, the backward step the one-site apply of update_site
+// (direction 0) under the same exponential; the state stays normalised and the growth factors are handed out as logarithms.
+// =====================================================================================================================
+int htn_mps::evolve_checks(const htn_sweep_opts& o, const char* who) const {
+    if (ctx->world > 1 || ctx->shard || ctx->exch || be->has_comm())
+        return set_error("%s: time evolution on a context with a communicator or an exchange hook is not supported", who);
+    if (!orth.empty()) return set_error("%s: time evolution of a state with attached orthogonal states is not supported", who);
+    if (Llay[0]->size != 0 || Rlay[L]->size != 0)
+        return set_error("%s: time evolution of a chain with boundary environments (an iDMRG window) is not supported", who);
+    if (o.krylovdim < 2 || o.krylovdim > 31) return set_error("%s: krylovdim = %d (must be in 2..31)", who, o.krylovdim);
+    return 0;
+}
+
+int htn_mps::evolve_site(int i, cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* log_growth) {
+    if (evolve_checks(o, "htn_site_evolve") || site1_checks(this, i, "htn_site_evolve")) return 1;
+    StageClock clk(be, o.profile);
+    const SiteLayoutP lay = site_lay[i];
+    Solve s;
+    const int64_t n = s.n = lay->size;
+    if (n <= 0) return set_error("htn_site_evolve: empty site tensor on site %d", i);
+    const int kd = o.krylovdim;
+    DView V = zalloc((int64_t)(kd + 2) * n, false);
+    if (!V.base) return set_error("device allocation of the Krylov basis failed (%lld elements)", (long long)((kd + 2) * n));
+    if (relay(*lay, site_buf[i].ptr(), *lay, V.ptr())) return 1;
+    s.ap = make_apply1(i, *lay);
+    if (!s.ap) return 1;
+    DView z = zalloc(s.ap->zsize, false);
+    if (!z.base) return set_error("device allocation failed (one-site apply)");
+    htn_gemm_launch stages[2];
+    const int ns = apply_stages(*s.ap, Lbuf[i], Rbuf[i + 1], z, stages);
+    if (ns < 0) return 1;
+    clk.plan = clk.lap();
+    if (be->krylov_expm(stages, ns, BUF_X, BUF_Y, V.ptr(), n, kd, dt.real(), dt.imag(), o.lanczos_tol, o.maxrestart, 0, nullptr, ctx, &s.growth,
+                        &s.E, &s.nmv, &s.res, be->timing ? &s.mv_ms : nullptr))
+        return 1;
+    clk.lanczos = clk.lap();
+    DView out = zalloc(n, false);
+    if (!out.base) return set_error("device allocation failed (site tensor)");
+    if (relay(*lay, V.ptr(), *lay, out.ptr())) return 1;
+    site_buf[i] = out;
+    if (log_growth) *log_growth += log(s.growth);
+    if (st) fill_stats(st, i, 0, s, Llay[i]->size + Rlay[i + 1]->size, 0, 0, 0.0, clk);
+    return 0;
+}
+
+int htn_mps::tdvp2_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* E, double* log_norm) {
+    if (evolve_checks(o, "htn_tdvp2_sweep")) return 1;
+    if (L < 2) return set_error("htn_tdvp2_sweep: a chain of %d site(s) has no bond to sweep over", L);
+    if (centre != 0) return set_error("htn_tdvp2_sweep: the centre is on site %d, not on site 0", centre);
+    const cplx half = 0.5 * dt, back = -0.5 * dt;
+    double lg = 0.0;
+    htn_bond_stats site_st;
+    int k = 0;
+    auto bond = [&](int i, int direction, bool right, int site) -> int {
+        htn_bond_stats* rec = st ? st + k : nullptr;
+        ++k;
+        if (update_bond(i, direction, right, true, o, rec, &half, &lg)) return 1;
+        if (site < 0) return 0;
+        if (evolve_site(site, back, o, rec ? &site_st : nullptr, &lg)) return 1;
+        if (rec) rec->n_matvec += site_st.n_matvec, rec->t_total += site_st.t_total, rec->t_lanczos += site_st.t_lanczos;
+        return 0;
+    };
+    for (int i = 0; i < L - 1; ++i)
+        if (bond(i, +1, true, i < L - 2 ? i + 1 : -1)) return 1;
+    for (int i = L - 2; i >= 0; --i)
+        if (bond(i, -1, false, i > 0 ? i : -1)) return 1;
+    if (E) *E = energy;
+    if (log_norm) *log_norm = lg;
+    return 0;
+}
+
+// the quench: another Hamiltonian under the same state.  Everything that was planned or contracted with the old MPO goes (the
+// plan cache, the environments); the boundaries and the right environments are rebuilt as mps_finish builds them.
+static int mps_finish(htn_mps* e, const void* left_env_host, const void* right_env_host, const DView* left_dev, const DView* right_dev);
+int htn_mps::set_mpo(htn_mpo* m) {
+    const Mpo& nm = m->mpo;
+    if (m->ctx != ctx) return set_error("htn_mps_set_mpo: the MPO lives in a different context");
+    if ((int)nm.sites.size() != L) return set_error("htn_mps_set_mpo: the MPO has %d sites, the state %d", (int)nm.sites.size(), L);
+    const Sym &a = mpo->sym, &b = nm.sym;
+    bool same = a.kind == b.kind && a.n_site == b.n_site;
+    for (int q = 0; same && q < a.n_site; ++q) same = a.site[q] == b.site[q];
+    if (!same) return set_error("htn_mps_set_mpo: the MPO has a different symmetry or other site multiplets");
+    if (centre != 0) return set_error("htn_mps_set_mpo: the centre is on site %d, not on site 0", centre);
+    if (Llay[0]->size != 0 || Rlay[L]->size != 0 || nm.sites.front().left.size() != 1 || nm.sites.back().right.size() != 1)
+        return set_error("htn_mps_set_mpo: a chain with boundary environments (an iDMRG window) cannot change its Hamiltonian");
+    for (int i = 1; i < L; ++i)
+        if (site_lay[i]->kind != 'R') return set_error("htn_mps_set_mpo: site %d is not in right layout", i);
+    // the new environments are built first, with the old ones set aside: a failure puts everything back
+    htn_mpo* old = mpo_handle;
+    const Mpo* old_mpo = mpo;
+    auto old_cache = std::move(cache);
+    auto oLl = Llay, oRl = Rlay;
+    auto oLb = Lbuf, oRb = Rbuf;
+    ++m->refs;
+    mpo_handle = m;
+    mpo = &m->mpo;
+    cache.clear();
+    for (int b2 = 0; b2 <= L; ++b2) {
+        Llay[b2] = nullptr, Rlay[b2] = nullptr;
+        Lbuf[b2] = DView(), Rbuf[b2] = DView();
+    }
+    if (mps_finish(this, nullptr, nullptr, nullptr, nullptr)) {
+        mpo_handle = old;
+        mpo = old_mpo;
+        cache = std::move(old_cache);
+        Llay = oLl, Rlay = oRl, Lbuf = oLb, Rbuf = oRb;
+        mpo_release(m);
+        return 1;
+    }
+    mpo_release(old);
+    energy = NAN;                  // (no energy of the new Hamiltonian is known until an update reports one)
     return 0;
 }
 
@@ -2264,6 +2466,48 @@ int htn_dmrg1_sweep(htn_mps* mps, const htn_sweep_opts* opts, htn_bond_stats* st
     if (!mps) return set_error("htn_dmrg1_sweep: bad arguments");
     if (mps->be->activate()) return 1;
     return mps->sweep1(norm_opts(opts), stats, energy);
+}
+int htn_bond_evolve(htn_mps* mps, int32_t i, int32_t direction, int32_t placement, double dt_re, double dt_im, const htn_sweep_opts* opts,
+                    htn_bond_stats* stats) {
+    if (!mps) return set_error("htn_bond_evolve: bad arguments");
+    if (mps->be->activate()) return 1;
+    const htn_sweep_opts o = norm_opts(opts);
+    if (mps->evolve_checks(o, "htn_bond_evolve")) return 1;
+    const cplx dt(dt_re, dt_im);
+    return mps->update_bond(i, direction, placement == 0, true, o, stats, &dt, nullptr);
+}
+int htn_site_evolve(htn_mps* mps, int32_t i, double dt_re, double dt_im, const htn_sweep_opts* opts, htn_bond_stats* stats) {
+    if (!mps) return set_error("htn_site_evolve: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->evolve_site(i, cplx(dt_re, dt_im), norm_opts(opts), stats, nullptr);
+}
+int htn_tdvp2_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_opts* opts, htn_bond_stats* stats, double* energy,
+                    double* log_norm) {
+    if (!mps) return set_error("htn_tdvp2_sweep: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->tdvp2_sweep(cplx(dt_re, dt_im), norm_opts(opts), stats, energy, log_norm);
+}
+int htn_mps_set_mpo(htn_mps* mps, const htn_mpo* mpo) {
+    if (!mps || !mpo) return set_error("htn_mps_set_mpo: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->set_mpo(const_cast<htn_mpo*>(mpo));
+}
+// Host-memory statement of the kernel-level entry: what the CPU baseline library exports (V and the buffers of the stages are
+// host pointers, the stages run through that library's grouped GEMM, scratch and stream are not used).  Weak: in
+// libhubbardtn_hip.so the definition of htn_krylov.hip (device pointers, the gfx950 kernels) takes its place at link time.
+__attribute__((weak)) int htn_krylov_expm_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot, void* V, int64_t n,
+                                            int32_t krylovdim, double dt_re, double dt_im, double tol, int32_t max_restart, void* scratch,
+                                            int32_t zero_y, htn_exchange2_fn exchange, void* user, double* growth_host, double* alpha0_host,
+                                            int32_t* n_matvec_host, double* err_host, double* matvec_ms_host, void* stream) {
+    (void)scratch, (void)stream;
+    if (!stages || !V || !growth_host || !alpha0_host || !n_matvec_host || !err_host) return set_error("htn_krylov_expm_z: bad arguments");
+    std::unique_ptr<Backend> be(make_backend(HTN_BACKEND_CPU, 0, nullptr));
+    if (!be) return 1;
+    int nmv = 0;
+    const int rc = be->krylov_expm(stages, n_stages, x_slot, y_slot, V, n, krylovdim, dt_re, dt_im, tol, max_restart, zero_y, exchange, user,
+                                   growth_host, alpha0_host, &nmv, err_host, matvec_ms_host);
+    *n_matvec_host = nmv;
+    return rc;
 }
 int32_t htn_mps_centre(const htn_mps* mps) { return mps->centre; }
 int64_t htn_mps_site_theta_size(htn_mps* mps, int32_t i) {

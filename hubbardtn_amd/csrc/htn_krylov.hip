@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "htn_common.h"
+#include "htn_expm.h"
 
 #define DOT_BLOCKS HTN_DOT_BLOCKS   // partial sums per vector = slices of the vector (4 per lane of the reducing wave)
 #define DOT_THREADS 256       // threads of the axpy / scale kernels
@@ -461,9 +462,43 @@ __global__ __launch_bounds__(256) void k_scale_inv_sqrt(double2* __restrict__ ds
     }
 }
 
+// Krylov exponential (htn_krylov_expm_z): V[0] <- sum_i c_i V[i] in place, i < nvec, for an ORTHONORMAL basis and host
+// coefficients already divided by |c|_2 -- the result has norm 1 without a norm pass.  The coefficients travel BY VALUE in the
+// kernel arguments (32 double2 = 512 B: no staging buffer, no copy, nothing to drain before it is reused).  One launch; it
+// reads nvec n 16 B and writes n 16 B.  A thread reads its element of every row (CH 16-byte loads in flight, coalesced down
+// each row; rows past nvec are clamped re-reads with coefficient 0) BEFORE it writes its element of row 0, and no other
+// thread touches that element: the in-place update is safe.
+struct KrylovCoef {
+    double2 c[DOT_CHUNK];
+};
+template <int CH, int TH>
+__global__ __launch_bounds__(TH) void k_krylov_combine(double2* V, int64_t ldv, int nvec, int64_t n, const KrylovCoef kc) {
+    for (int64_t j = (int64_t)blockIdx.x * TH + threadIdx.x; j < n; j += (int64_t)gridDim.x * TH) {
+        double2 v[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int i = c < nvec ? c : nvec - 1;
+            v[c] = V[(int64_t)i * ldv + j];
+        }
+        double sr = 0.0, si = 0.0;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {                    // kc.c[c] = 0 beyond nvec
+            sr += kc.c[c].x * v[c].x - kc.c[c].y * v[c].y;
+            si += kc.c[c].x * v[c].y + kc.c[c].y * v[c].x;
+        }
+        V[j] = make_double2(sr, si);
+    }
+}
+
 static inline int grid_for(int64_t n) {
     int64_t b = (n + 255) / 256;
     return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
+}
+
+static void launch_krylov_combine(double2* V, int64_t ldv, int nvec, int64_t n, const KrylovCoef& kc, hipStream_t st) {
+#define HTN_KC(CHV, THV) hipLaunchKernelGGL((k_krylov_combine<CHV, THV>), dim3(grid_for(n)), dim3(THV), 0, st, V, ldv, nvec, n, kc)
+    HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_KC);
+#undef HTN_KC
 }
 
 extern "C" int64_t htn_dots_scratch_elems(int32_t nvec) { return (int64_t)nvec * DOT_BLOCKS; }
@@ -620,7 +655,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
                        void* Vv, int64_t n, int32_t krylovdim, double tol, int32_t max_restart,
                        void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
                        double* eig_host, int32_t* n_matvec_host, double* residual_host,
-                       double* matvec_ms_host, void* stream_v, const double2* Q, int nf) {
+                       double* matvec_ms_host, void* stream_v, const double2* Q, int nf, htn_expm::Expm* ex = nullptr) {
     hipStream_t st = (hipStream_t)stream_v;
     const int kd = krylovdim;
     const int kt = kd + nf;                                        // rows of the widest pass + 1
@@ -639,6 +674,8 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
 
     bool timed_step[LAN_SLOTS] = {false};
     unsigned long long step_serial[LAN_SLOTS] = {0};
+    // (expm with dt = 0: the identity needs alpha_0 only -- one step that publishes its own record, nothing speculative)
+    const bool solo = ex && ex->dt_re == 0.0 && ex->dt_im == 0.0;
     auto matvec = [&](double2* x, double2* y, const HtnGemmPublish* pub) -> int {
         if (zero_y) HIP_TRY(hipMemsetAsync(y, 0, sizeof(double2) * n, st));
         bool published = pub == nullptr;
@@ -694,7 +731,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
                                 first ? (const double*)nullptr : norm_partial, nf + upd0, Q, nf, st);
             launch_axpy_norm_fz(w, V, n, nf + j + 1, partial2, c2 + j, nf + j, -1.0, n, norm_partial, Q, nf, st);
         }
-        if (j == kd - 1) {
+        if (j == kd - 1 || solo) {
             hipLaunchKernelGGL(k_publish_record, dim3(1), dim3(64), 0, st, (const double*)norm_partial, (const double2*)(c1 + j),
                                (const double2*)(c2 + j), R->d_rec + j, step_serial[j]);
             if (event_waits) HIP_TRY(hipEventRecord(R->ev_done[j], st));
@@ -756,6 +793,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
     std::vector<double> y;
     for (int restart = 0; restart <= max_restart; ++restart) {
         std::vector<double> alphas, betas;
+        if (ex) ex->begin_cycle();
         // Software pipeline of depth 1: step j+1 is enqueued BEFORE the host waits for step j's record, so the
         // GPU never idles during the host's convergence test.  If step j converges, step j+1 was speculative:
         // it only wrote Krylov row j+2, device scalars j+1 and record slot j+1, which nothing reads afterwards.
@@ -764,7 +802,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
         t_enq += now_us() - tq;
         ++nmv;
         for (int j = 0; j < kd; ++j) {
-            if (j + 1 < kd) {
+            if (j + 1 < kd && !solo) {
                 tq = now_us();
                 if (enqueue_step(j + 1, false)) return 1;
                 t_enq += now_us() - tq;
@@ -785,6 +823,14 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
             const double alpha = a1 + a2;
             if (!(alpha == alpha) || !(nn == nn)) return fail_msg("htn_lanczos_z: NaN in the tridiagonal coefficients (operator or start vector not finite)");
             beta = sqrt(nn > 0.0 ? nn : 0.0);
+            if (ex) {
+                bool bad = false;
+                const bool stop = ex->step(alpha, beta, kd, &bad);
+                if (bad) return fail_msg("htn_krylov_expm_z: the QL iteration of the tridiagonal matrix did not converge");
+                t_host += now_us() - tq;
+                if (stop) break;
+                continue;
+            }
             alphas.push_back(alpha);
             tridiag_lowest(alphas, betas, &theta, y);
             res = fabs(beta * y.back());
@@ -793,6 +839,30 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
             t_host += now_us() - tq;
             if (res < tol || beta < 1e-14 * std::max(amax, 1e-300) || j == kd - 1) break;
             betas.push_back(beta);
+        }
+        if (ex) {
+            // The step of this cycle in one launch.  No drain: the speculative step wrote row m + 1, the combination reads rows
+            // 0 .. m - 1 and everything is ordered on the stream; its record, if it still arrives, fails the serial check.
+            // INVARIANT FOR CALLERS: unlike the eigen-solver path (two drains per cycle), this path RETURNS with the speculative
+            // step and the combination still in flight on `st`.  Whatever touches V, the scratch or the stage buffers next --
+            // reading the result, handing the blocks back to a pool, the next solve -- must be ordered on the same stream (the
+            // engine's pool, relay and downloads are; torch's allocator is for its current stream) or wait for it.
+            if (!ex->converged && restart == max_restart) {
+                HIP_TRY(htn_stream_spin(st));
+                snprintf(htn_err_buf(), 512, "htn_krylov_expm_z: not converged after %d restart(s) of krylovdim %d: fraction %.3e of dt remains "
+                         "(estimate %.3e, tol %.3e)", max_restart, kd, ex->remaining, ex->est, tol);
+                return 1;
+            }
+            if (!ex->finish()) {
+                HIP_TRY(htn_stream_spin(st));
+                return fail_msg("htn_krylov_expm_z: no fraction of the step down to 2^-60 meets the tolerance");
+            }
+            const int m = (int)ex->c.size();
+            KrylovCoef kc;
+            for (int i = 0; i < DOT_CHUNK; ++i) kc.c[i] = i < m ? make_double2(ex->c[i].real(), ex->c[i].imag()) : make_double2(0.0, 0.0);
+            launch_krylov_combine(V, n, m, n, kc, st);
+            if (ex->remaining == 0.0) break;
+            continue;
         }
         HIP_TRY(htn_stream_spin(st));       // drain the speculative step before rows are reused
         // x = sum_i y_i V_i  -> scratch row kd+1, normalised into row 0
@@ -816,9 +886,9 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
     if (dbg_timers)
         fprintf(stderr, "lanczos n=%lld: %d matvecs in %.1f us: enqueue %.1f, waiting for records %.1f, tridiagonal %.1f\n", (long long)n, nmv,
                 now_us() - t_begin, t_enq, t_wait, t_host);
-    *eig_host = theta;
+    *eig_host = ex ? ex->alpha0 : theta;
     *n_matvec_host = nmv;
-    *residual_host = res;
+    *residual_host = ex ? ex->err_total : res;
     // sampled launches scaled to all launches of this solve (the next solves continue the 1-in-8 sampling phase)
     if (matvec_ms_host) *matvec_ms_host = n_timed ? mv_ms * nmv / n_timed : -1.0;
     return 0;
@@ -846,4 +916,36 @@ extern "C" int htn_lanczos_orth_z(const htn_gemm_launch* stages, int32_t n_stage
         return fail_msg("htn_lanczos_orth_z: krylovdim >= 2 and krylovdim + n_frozen <= 31 required");
     return lanczos_run(stages, n_stages, x_slot, y_slot, Vv, n, krylovdim, tol, max_restart, scratch, zero_y, exchange, user,
                        eig_host, n_matvec_host, residual_host, matvec_ms_host, stream_v, (const double2*)Q, n_frozen);
+}
+
+// V[0] <- sum_i coef[i] V[i] in place (hubbardtn_hip.h): the combine launch on its own
+extern "C" int htn_krylov_combine_z(void* V, int64_t ldv, int32_t nvec, const double* coef_host, int64_t n, void* stream) {
+    if (nvec < 1 || nvec > DOT_CHUNK) return fail_msg("htn_krylov_combine_z: nvec must be in 1..32");
+    if (!V || !coef_host || n < 0 || ldv < n) return fail_msg("htn_krylov_combine_z: bad arguments (V, coef_host, 0 <= n <= ldv)");
+    if (n == 0) return 0;
+    KrylovCoef kc;
+    for (int i = 0; i < DOT_CHUNK; ++i) kc.c[i] = i < nvec ? make_double2(coef_host[2 * i], coef_host[2 * i + 1]) : make_double2(0.0, 0.0);
+    launch_krylov_combine((double2*)V, ldv, nvec, n, kc, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// x = exp(-i dt H) x0 through the basis lanczos_run builds (hubbardtn_hip.h; the host decisions are htn_expm::Expm's)
+extern "C" int htn_krylov_expm_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot, void* Vv, int64_t n,
+                                 int32_t krylovdim, double dt_re, double dt_im, double tol, int32_t max_restart, void* scratch,
+                                 int32_t zero_y, htn_exchange2_fn exchange, void* user, double* growth_host, double* alpha0_host,
+                                 int32_t* n_matvec_host, double* err_host, double* matvec_ms_host, void* stream_v) {
+    if (krylovdim < 2 || krylovdim + 1 > DOT_CHUNK) return fail_msg("htn_krylov_expm_z: krylovdim must be in 2..31");
+    if (!Vv || !scratch || n <= 0 || !growth_host || !alpha0_host || !n_matvec_host || !err_host) return fail_msg("htn_krylov_expm_z: bad arguments");
+    if (!(dt_re == dt_re) || !(dt_im == dt_im) || !(tol >= 0.0)) return fail_msg("htn_krylov_expm_z: dt and tol must be finite, tol >= 0");
+    htn_expm::Expm ex;
+    ex.dt_re = dt_re, ex.dt_im = dt_im, ex.tol = tol;
+    double a0 = 0.0, err = 0.0;
+    if (lanczos_run(stages, n_stages, x_slot, y_slot, Vv, n, krylovdim, tol, max_restart < 0 ? 0 : max_restart, scratch, zero_y, exchange,
+                    user, &a0, n_matvec_host, &err, matvec_ms_host, stream_v, nullptr, 0, &ex))
+        return 1;
+    *growth_host = ex.growth;
+    *alpha0_host = a0;
+    *err_host = err;
+    return 0;
 }

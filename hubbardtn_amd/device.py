@@ -269,6 +269,37 @@ class HipOps:
             self.event_log.append(("matvec_ms", ms.value, nmv.value))
         return eig.value, nmv.value, res.value
 
+    def krylov_combine(self, V, ldv, nvec, coef, n):
+        """htn_krylov_combine_z: V[0:n] <- sum_{i < nvec} coef[i] V[i * ldv : i * ldv + n] in place, one launch; coef: host
+        complex array (passed to the kernel by value)"""
+        c = np.ascontiguousarray(coef, dtype=np.complex128)
+        assert c.shape == (nvec,)
+        abi.check(self.lib, self.lib.htn_krylov_combine_z(self._p(V), int(ldv), int(nvec), c.ctypes.data, int(n), self._stream()),
+                  "htn_krylov_combine_z")
+
+    def krylov_expm(self, stages, x_slot, y_slot, V, n, krylovdim, dt, tol, max_restart, zero_y=False):
+        """htn_krylov_expm_z: V[0:n] <- exp(-i dt H) V[0:n], normalised, for the Hermitian map defined by `stages` (as for
+        lanczos); dt complex (dt = -i beta: imaginary time).  Returns (growth = |x| / |x0|, alpha0 = <x0|H|x0> / |x0|^2,
+        n_matvec, error estimate)."""
+        arr = (abi.GemmLaunch * len(stages))()
+        keep = []
+        for k, (bufs, (tiles, ntiles, segs)) in enumerate(stages):
+            for b in range(abi.HTN_MAX_BUFS):
+                arr[k].bufs[b] = 0 if bufs[b] is None else bufs[b].data_ptr()
+            arr[k].tiles, arr[k].segs, arr[k].n_tiles = tiles.data_ptr(), segs.data_ptr(), ntiles
+            keep.append((bufs, tiles, segs))
+        need = self.lib.htn_lanczos_scratch_elems(max(int(krylovdim), 2))
+        if getattr(self, "_lan_scratch", None) is None or self._lan_scratch.numel() < need:
+            self._lan_scratch = self.empty_z(need)
+        dt = complex(dt)
+        growth, a0, nmv, err = C.c_double(0.0), C.c_double(0.0), C.c_int32(0), C.c_double(0.0)
+        rc = self.lib.htn_krylov_expm_z(arr, len(stages), x_slot, y_slot, self._p(V), n, int(krylovdim), dt.real, dt.imag,
+                                        float(tol), int(max_restart), self._p(self._lan_scratch), 1 if zero_y else 0,
+                                        abi.EXCHANGE_FN(), None, C.byref(growth), C.byref(a0), C.byref(nmv), C.byref(err),
+                                        None, self._stream())
+        abi.check(self.lib, rc, "htn_krylov_expm_z")
+        return growth.value, a0.value, nmv.value, err.value
+
     def jacobi_svd(self, G, Vj, S, desc_dev, nblocks, max_m, max_sweeps, tol, info, desc_host=None, split=0, rank_cut=0.0,
                    sweeps_hint=0):
         """split: elements of R^H above which a block takes the large-block SVD path (0 = default);

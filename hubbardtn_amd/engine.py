@@ -451,6 +451,68 @@ class DMRG2:
         self.energy = E.value
         return self.energy
 
+    # ---- time evolution: two-site TDVP (htn_bond_evolve / htn_site_evolve / htn_tdvp2_sweep / htn_mps_set_mpo) ----
+    def evolve_bond(self, i, direction, placement, dt, record=True):
+        """theta <- exp(-i dt H_eff) theta on sites (i, i+1), then SVD, truncation, write-back and environment move as
+        update_bond; dt complex (-i beta: imaginary time).  -> BondStats (energy = <theta|H_eff|theta> before the step,
+        residual = the error estimate of the exponential)"""
+        self.__dict__.pop("_bond_cache", None)
+        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
+        o, dt = self._opts(), complex(dt)
+        self._check(self.lib.htn_bond_evolve(self.handle, i, direction, 0 if placement == "right" else 1, dt.real, dt.imag,
+                                             C.byref(o), st.ctypes.data), "htn_bond_evolve")
+        s = _stats(st[0])
+        if record:
+            self.stats.append(s)
+            self.energy = s.energy
+        return s
+
+    def evolve_site(self, i, dt, record=True):
+        """centre on site i <- exp(-i dt H_eff1) centre in place (no gauge move); -> BondStats"""
+        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
+        o, dt = self._opts(), complex(dt)
+        self._check(self.lib.htn_site_evolve(self.handle, i, dt.real, dt.imag, C.byref(o), st.ctypes.data), "htn_site_evolve")
+        s = _stats(st[0])
+        if record:
+            self.stats.append(s)
+        return s
+
+    def tdvp_sweep(self, dt):
+        """one symmetric two-site TDVP step of length dt (complex; -i beta: imaginary time), one library call: half steps on
+        the bonds rightwards and leftwards with backward one-site steps between them (2L-2 bond records).  The centre starts and
+        ends on site 0, the state stays normalised; `log_norm` holds the logarithm of the norm change the exponentials produced
+        (0 for real dt), `trunc_weights` the discarded weight per record.  lanczos_tol is the tolerance of the exponential.
+        Returns <psi|H|psi> as the last bond step saw it."""
+        self.__dict__.pop("_bond_cache", None)
+        n = 2 * self.L - 2
+        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
+        E, lg = C.c_double(0.0), C.c_double(0.0)
+        o, dt = self._opts(), complex(dt)
+        self._check(self.lib.htn_tdvp2_sweep(self.handle, dt.real, dt.imag, C.byref(o), st.ctypes.data, C.byref(E), C.byref(lg)),
+                    "htn_tdvp2_sweep")
+        self.stats.extend(_stats(r) for r in st)
+        self.energy = E.value
+        self.log_norm = lg.value
+        return self.energy
+
+    def set_mpo(self, mpo):
+        """swap the Hamiltonian under the state (a quench): same symmetry, chain length and site multiplets, centre on site
+        0.  The environments are rebuilt on the device; the tensors are not touched."""
+        cm = mpo if isinstance(mpo, CMpo) else CMpo(self.ops, mpo)
+        self._check(self.lib.htn_mps_set_mpo(self.handle, cm.handle), "htn_mps_set_mpo")
+        self.cmpo, self.mpo = cm, cm.sites
+        self.energy = None
+
+    def copy(self):
+        """a second, independent engine holding the same state (bonds() + download_site through the constructor).  Call with
+        the centre on site 0 (after construction or a sweep)."""
+        if self.centre() != 0:
+            raise ValueError("DMRG2.copy: the centre must be on site 0")
+        tensors = [self.download_site(i) for i in range(self.L)]
+        bonds = [dict(b.dims) for b in self.bonds]
+        return DMRG2(self.ops, self.cmpo, bonds, tensors, self.chi_full, self.cutoff, self.krylovdim, self.lanczos_tol,
+                     self.maxrestart, self.weighting, self.jacobi_tol, self.jacobi_max_sweeps)
+
     def apply_heff1(self, i, x):
         """y = H_eff(site i) x on host vectors in the stored layout of site i (the flat vector of `download_site`'s
         blocks: htn_mps_get_site); the centre must be on site i"""

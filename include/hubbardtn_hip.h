@@ -149,6 +149,32 @@ int htn_lanczos_orth_z(const htn_gemm_launch* stages_host, int32_t n_stages, int
                        double* eig_host, int32_t* n_matvec_host, double* residual_host, double* matvec_ms_host,
                        const void* Q, int32_t n_frozen, void* stream);
 
+/* Krylov exponential: x = exp(-i dt H) x0 for the Hermitian map given as stages (as for htn_lanczos_z), dt = dt_re + i dt_im
+ * (dt = -i beta is imaginary time: exp(-beta H)).  Stands in for KrylovKit.exponentiate(H_eff, -i dt, x0, Lanczos(...)) as
+ * MPSKit's TDVP2 calls it.  The orthonormal basis is built by the step kernels and the depth-1 pipeline of htn_lanczos_z; after
+ * step m the host diagonalises the real tridiagonal T_m completely (implicit QL, m <= 31), forms c = exp(-i dt T_m) e_1 and
+ * Saad's a-posteriori estimate est = beta_m |dt| |c_m|, and stops at the first m with est < tol, with beta_m < 1e-14 x (largest
+ * |alpha| or beta seen: an invariant subspace, the result is exact), or at m = krylovdim.  Not converged at krylovdim: the
+ * fraction s of the remaining time is halved until beta_m |s dt| |c_m(s dt)| < tol s (host work on the same T), that partial
+ * step is applied and the basis is rebuilt from its result for the remaining time (the tolerance of later cycles is scaled by
+ * the fraction that remains); at most max_restart restarts, then the call fails and the error names the fraction that remains.
+ * Every step is applied by ONE launch, V[0] <- sum_i (c_i / |c|) V[i] in place (the basis is orthonormal, so the norm is known
+ * on the host; the coefficients travel in the kernel arguments).  Nothing but the step records is read back.
+ * V, scratch, krylovdim (2..31), zero_y, exchange: as for htn_lanczos_z.  On exit V[0:n] = x / |x|,
+ * *growth_host = |x| / |x0| (1 to rounding for real dt), *alpha0_host = <x0|H|x0> / |x0|^2 (the first Lanczos alpha),
+ * *err_host = the sum of the estimates of the steps applied, *n_matvec_host = matvecs enqueued (speculative ones included).
+ * dt = 0: one matvec (alpha0), x = x0 / |x0|.  The CPU baseline library exports the symbol with host pointers and no kernels
+ * (full two-pass reorthogonalisation, the same decisions). */
+/* The combine launch of htn_krylov_expm_z on its own: V[0:n] <- sum_{i < nvec} coef[i] V[i * ldv : i * ldv + n] in place, nvec in
+ * 1..32, coef_host = nvec complex128 (re, im pairs) in HOST memory, passed to the kernel by value: nothing is staged, the array may
+ * be reused as soon as the call returns.  Rows 1.. are only read.  HIP library only. */
+int htn_krylov_combine_z(void* V, int64_t ldv, int32_t nvec, const double* coef_host, int64_t n, void* stream);
+int htn_krylov_expm_z(const htn_gemm_launch* stages_host, int32_t n_stages, int32_t x_slot, int32_t y_slot,
+                      void* V, int64_t n, int32_t krylovdim, double dt_re, double dt_im, double tol,
+                      int32_t max_restart, void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
+                      double* growth_host, double* alpha0_host, int32_t* n_matvec_host, double* err_host,
+                      double* matvec_ms_host, void* stream);
+
 /* Batched one-sided Jacobi SVD of the coupled-sector blocks of a two-site tensor.
  * Stands in for: TensorKit tsvd!(t; alg=SVD()) -> LAPACK zgesvd per block (SURVEY.md 8a a9,
  * scheme chosen at src/HubbardFunctions.jl:1010 and :1363-1365).
@@ -456,6 +482,36 @@ int32_t htn_mps_centre(const htn_mps* mps);
  * sub-block table: htn_mps_get_site); the centre must be on site i.  Tests and Hermiticity checks. */
 int64_t htn_mps_site_theta_size(htn_mps* mps, int32_t i);
 int htn_heff1_apply(htn_mps* mps, int32_t i, const void* x_host, void* y_host);
+
+/* Time evolution of a finite chain: two-site TDVP (Haegeman et al., Phys. Rev. B 94, 165116; MPSKit's TDVP2).  dt = dt_re + i dt_im
+ * travels as arguments (htn_sweep_opts keeps its layout); dt = -i beta evolves in imaginary time.  From opts: the truncation,
+ * krylovdim (2..31), lanczos_tol (the tolerance of htn_krylov_expm_z), maxrestart, the SVD settings.
+ * htn_bond_evolve: htn_bond_update with the eigen-solve replaced by theta <- exp(-i dt H_eff2) theta; SVD, truncation by opts,
+ *   write-back (placement as there) and environment move are the same, the centre is renormalised after the truncation.
+ *   stats: energy = <theta|H_eff2|theta> BEFORE the step (the first Lanczos alpha), residual = the error estimate, n_matvec,
+ *   trunc_weight.  The norm change |x| / |x0| of the exponential is NOT returned by htn_bond_evolve / htn_site_evolve (the state is
+ *   renormalised and htn_bond_stats has no field for it): a caller who needs it -- imaginary time -- uses htn_tdvp2_sweep, whose
+ *   log_norm_host sums it over the sweep.
+ * htn_site_evolve: the centre must be on site i; exp(-i dt H_eff1) on the stored site vector in place (the one-site stages of
+ *   htn_site_update with direction 0): no QR, the centre stays.
+ * htn_tdvp2_sweep: one symmetric second-order step of length dt.  Rightwards i = 0 .. L-2: bond_evolve(i, dt/2) placement right,
+ *   then (i < L-2) site_evolve(i+1, -dt/2); leftwards i = L-2 .. 0: bond_evolve(i, dt/2) placement left, then (i > 0)
+ *   site_evolve(i, -dt/2).  The centre must be on site 0 and ends there.  stats_host: 2L-2 records or NULL, the n_matvec of a
+ *   record includes the backward site step that follows it; energy_host = the last record's energy; log_norm_host (may be
+ *   NULL) = the sum of log(|x| / |x0|) over all solves of the sweep (the state itself stays normalised; 0 to rounding for real dt).
+ * htn_mps_set_mpo: swaps the Hamiltonian of an existing state (a quench).  Same context, symmetry, chain length and site
+ *   multiplets; the centre on site 0; open ends (no boundary environments).  The right environments are rebuilt on the device as
+ *   htn_mps_create builds them and the plan cache is dropped; the state's tensors are not touched.  If building them fails the
+ *   call returns the error and the state keeps its old Hamiltonian, environments and plans.  The state holds a counted
+ *   reference to the new MPO and drops the one to the old.
+ * Refused: contexts with a communicator or an exchange hook, states with attached orthogonal states, iDMRG windows,
+ * krylovdim outside 2..31. */
+int htn_bond_evolve(htn_mps* mps, int32_t i, int32_t direction, int32_t placement, double dt_re, double dt_im,
+                    const htn_sweep_opts* opts, htn_bond_stats* stats_host);
+int htn_site_evolve(htn_mps* mps, int32_t i, double dt_re, double dt_im, const htn_sweep_opts* opts, htn_bond_stats* stats_host);
+int htn_tdvp2_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_opts* opts, htn_bond_stats* stats_host,
+                    double* energy_host, double* log_norm_host);
+int htn_mps_set_mpo(htn_mps* mps, const htn_mpo* mpo);
 
 /* Excited states inside one sector: orthogonalised two-site DMRG.  After htn_mps_set_orthogonal(mps, others, n) every
  * OPTIMISING bond update of `mps` finds the lowest eigenpair of H_eff inside the orthogonal complement of the n attached
