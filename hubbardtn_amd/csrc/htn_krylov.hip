@@ -11,6 +11,7 @@
 // 64 partials with a butterfly), so results are bit-reproducible run to run and rank to rank.
 #include <math.h>
 
+#include <atomic>
 #include <chrono>
 #include <vector>
 
@@ -597,7 +598,8 @@ static void tridiag_lowest(const std::vector<double>& alpha, const std::vector<d
 }
 
 extern "C" int64_t htn_lanczos_scratch_elems(int32_t krylovdim) {
-    // 2 x partial sums (krylovdim+1 vectors) + c1 + c2 + y (each krylovdim+1) + norm partials (as doubles)
+    // 2 x partial sums (krylovdim+1 vectors) + c1 + c2 + y (each krylovdim+1) + norm partials (as doubles); the y block is
+    // no longer written (the Ritz coefficients travel in the kernel arguments) and keeps its place in the layout
     return 2 * (int64_t)(krylovdim + 1) * DOT_BLOCKS + 3 * (krylovdim + 1) + DOT_BLOCKS + 8;
 }
 
@@ -608,7 +610,6 @@ struct LanRes {
     int device = -1;
     LanRecord* h_rec = nullptr;      // [LAN_SLOTS] host view  \ hipHostMallocMapped | hipHostMallocCoherent: written by the
     LanRecord* d_rec = nullptr;      //             device view / device only, read by the host only
-    double2* h_y = nullptr;          // Ritz coefficients, host -> device staging (a SEPARATE allocation)
     hipEvent_t ev_done[LAN_SLOTS], ev_mv0[LAN_SLOTS], ev_mv1[LAN_SLOTS];
     bool have_events = false;
     unsigned long long serial = 0;   // last step serial handed out; never reused within the life of the entry
@@ -616,7 +617,6 @@ struct LanRes {
     ~LanRes() {
         if (device >= 0) (void)hipSetDevice(device);
         if (h_rec) (void)hipHostFree(h_rec);
-        if (h_y) (void)hipHostFree(h_y);
         if (have_events)
             for (int i = 0; i < LAN_SLOTS; ++i) {
                 (void)hipEventDestroy(ev_done[i]);
@@ -632,7 +632,6 @@ int lan_res_get(hipStream_t st, LanRes** out) {
         HIP_TRY(hipHostMalloc((void**)&r.h_rec, sizeof(LanRecord) * LAN_SLOTS, hipHostMallocMapped | hipHostMallocCoherent));
         memset(r.h_rec, 0, sizeof(LanRecord) * LAN_SLOTS);      // (before any device work can see the block)
         HIP_TRY(hipHostGetDevicePointer((void**)&r.d_rec, r.h_rec, 0));
-        HIP_TRY(hipHostMalloc((void**)&r.h_y, sizeof(double2) * LAN_SLOTS, hipHostMallocDefault));
         for (int i = 0; i < LAN_SLOTS; ++i) {
             HIP_TRY(hipEventCreateWithFlags(&r.ev_done[i], hipEventDisableTiming));
             HIP_TRY(hipEventCreate(&r.ev_mv0[i]));
@@ -645,6 +644,36 @@ int lan_res_get(hipStream_t st, LanRes** out) {
 }  // namespace
 
 void htn_krylov_release_stream(hipStream_t st) { g_lan_res.release(st); }
+
+// ---- closing a solve at the step that is expected to converge -------------------------------------------------------------
+// An OPEN step is followed by the next step before the host has seen its record (the next step's first matvec launch carries
+// the record): if it converges, the step behind it ran for nothing -- the most expensive step of the solve.  A CLOSED step is
+// followed by k_publish_record and nothing else until the host has its record: if it converges no launch was wasted, if it does
+// not the GPU idles for one host round trip before the next step arrives.
+//   HTN_LANCZOS_CLOSE (read once per process)   unset / auto: the predictor below decides, step by step
+//                                               never:        every step is open but the last of a cycle
+//                                               always:       every step is closed (slow: a round trip per step)
+enum LanClose { LAN_CLOSE_AUTO, LAN_CLOSE_NEVER, LAN_CLOSE_ALWAYS };
+static LanClose lan_close_mode() {
+    static const LanClose mode = [] {
+        const char* v = getenv("HTN_LANCZOS_CLOSE");
+        if (v && !strcmp(v, "never")) return LAN_CLOSE_NEVER;
+        if (v && !strcmp(v, "always")) return LAN_CLOSE_ALWAYS;
+        return LAN_CLOSE_AUTO;
+    }();
+    return mode;
+}
+// Is the step after those whose residuals |beta y_last| are in `res` expected to converge?  Geometric extrapolation of the last
+// two residuals.  A pure function of the records and tol: every rank of a multi-rank run takes the same decision, and tol = 0
+// never closes.
+static bool lan_expect_convergence(const std::vector<double>& res, double tol) {
+    const size_t k = res.size();
+    if (k < 2) return false;
+    const double r0 = res[k - 2], r1 = res[k - 1];
+    return r1 < r0 && r1 * (r1 / r0) < tol;
+}
+// process totals for HTN_DEBUG_HOST_TIMERS: closed steps that converged / that did not; convergences at an open step
+static std::atomic<long long> g_lan_close_hit{0}, g_lan_close_miss{0}, g_lan_open_conv{0};
 
 // The driver of htn_lanczos_z (nf = 0) and htn_lanczos_orth_z (nf frozen rows Q: lowest eigenpair of P H P, P = 1 - Q Q^H).
 // With frozen rows every pass of a step runs over Q followed by the Krylov rows: the first (short) pass takes the dots with
@@ -672,7 +701,9 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
     const bool event_waits = htn_debug_event_waits();
     static const bool full_first_pass = htn_env_flag("HTN_LANCZOS_FULL_FIRST_PASS");
 
+    const LanClose close_mode = ex ? LAN_CLOSE_NEVER : lan_close_mode();
     bool timed_step[LAN_SLOTS] = {false};
+    bool closed[LAN_SLOTS] = {false};             // the step published its own record (k_publish_record)
     unsigned long long step_serial[LAN_SLOTS] = {0};
     // (expm with dt = 0: the identity needs alpha_0 only -- one step that publishes its own record, nothing speculative)
     const bool solo = ex && ex->dt_re == 0.0 && ex->dt_im == 0.0;
@@ -697,22 +728,31 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
     // V[j+1] with its squared norm in norm_partial.  For j > 0 (inside a cycle) V[j] itself is still the raw vector of step
     // j - 1: its normalisation is folded into this step's first update (k_axpy_dots, norm_prev) and the record of step j - 1 is
     // published by this step's first matvec launch -- four kernels per step instead of five.  The last step of a cycle
-    // publishes its own record (nothing follows it).  `first` = V[j] is already normalised (start / Ritz vector).
-    auto enqueue_step = [&](int j, bool first) -> int {
+    // publishes its own record (nothing follows it).  `first` = V[j] is already normalised (start / Ritz vector).  `carry` = this
+    // step's first matvec launch publishes the record of step j - 1 (false behind a closed step: that record has been delivered).
+    auto publish_step = [&](int j) -> int {
+        hipLaunchKernelGGL(k_publish_record, dim3(1), dim3(64), 0, st, (const double*)norm_partial, (const double2*)(c1 + j),
+                           (const double2*)(c2 + j), R->d_rec + j, step_serial[j]);
+        if (event_waits) HIP_TRY(hipEventRecord(R->ev_done[j], st));
+        closed[j] = true;
+        return 0;
+    };
+    auto enqueue_step = [&](int j, bool first, bool carry) -> int {
         double2* vj = V + (int64_t)j * n;
         double2* w = V + (int64_t)(j + 1) * n;
         // HIP events around a SAMPLE of the matvec launches (every 8th): an event is a marker packet that costs ~5 us
         // of pipeline bubble on this part, three of them per step were 15 us of a ~105 us Lanczos step
         const bool timed = matvec_ms_host && (R->sample % 8) == 0;
         timed_step[j] = timed;
+        closed[j] = false;
         ++R->sample;
         step_serial[j] = ++R->serial;
         HtnGemmPublish pub = {nullptr, nullptr, nullptr, nullptr, 0ull};
-        if (!first) pub = {norm_partial, (const double2*)(c1 + (j - 1)), (const double2*)(c2 + (j - 1)), R->d_rec + (j - 1), step_serial[j - 1]};
+        if (carry) pub = {norm_partial, (const double2*)(c1 + (j - 1)), (const double2*)(c2 + (j - 1)), R->d_rec + (j - 1), step_serial[j - 1]};
         if (timed) HIP_TRY(hipEventRecord(R->ev_mv0[j], st));
-        if (matvec(vj, w, first ? nullptr : &pub)) return 1;
+        if (matvec(vj, w, carry ? &pub : nullptr)) return 1;
         if (timed) HIP_TRY(hipEventRecord(R->ev_mv1[j], st));
-        if (!first && event_waits) HIP_TRY(hipEventRecord(R->ev_done[j - 1], st));
+        if (carry && event_waits) HIP_TRY(hipEventRecord(R->ev_done[j - 1], st));
         // Orthogonalisation in three kernels and TWO passes over the basis.  First the three-term part: dots with V[j-1]
         // and V[j] only, w' = w - V[j-1] c - V[j] c (against a basis that is orthonormal to rounding every other component
         // of H v_j is O(eps |H|): <v_i, H v_j> = conj(<v_j, H v_i>) and H v_i has no component along v_j for j > i + 1);
@@ -731,11 +771,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
                                 first ? (const double*)nullptr : norm_partial, nf + upd0, Q, nf, st);
             launch_axpy_norm_fz(w, V, n, nf + j + 1, partial2, c2 + j, nf + j, -1.0, n, norm_partial, Q, nf, st);
         }
-        if (j == kd - 1 || solo) {
-            hipLaunchKernelGGL(k_publish_record, dim3(1), dim3(64), 0, st, (const double*)norm_partial, (const double2*)(c1 + j),
-                               (const double2*)(c2 + j), R->d_rec + j, step_serial[j]);
-            if (event_waits) HIP_TRY(hipEventRecord(R->ev_done[j], st));
-        }
+        if (j == kd - 1 || solo) return publish_step(j);
         return 0;
     };
     // read slot j if it holds the record of THIS step (see LanRecord): true = accepted
@@ -792,22 +828,31 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
     double theta = 0.0, res = 0.0, beta = 0.0, amax = 0.0;
     std::vector<double> y;
     for (int restart = 0; restart <= max_restart; ++restart) {
-        std::vector<double> alphas, betas;
+        std::vector<double> alphas, betas, resids;
         if (ex) ex->begin_cycle();
         // Software pipeline of depth 1: step j+1 is enqueued BEFORE the host waits for step j's record, so the
         // GPU never idles during the host's convergence test.  If step j converges, step j+1 was speculative:
         // it only wrote Krylov row j+2, device scalars j+1 and record slot j+1, which nothing reads afterwards.
-        double tq = now_us();
-        if (enqueue_step(0, true)) return 1;
-        t_enq += now_us() - tq;
-        ++nmv;
+        // A step that is expected to converge is CLOSED instead (lan_expect_convergence): k_publish_record follows it, the host
+        // waits for the record, and nothing further is in flight.  If it did not converge after all, step j+1 follows as an
+        // ordinary non-first step -- row j+1 is raw, norm_partial holds its squared norm: the state an open step leaves -- only
+        // that its matvec carries no record.
+        int enq = 0;                              // steps of this cycle enqueued so far
         for (int j = 0; j < kd; ++j) {
-            if (j + 1 < kd && !solo) {
-                tq = now_us();
-                if (enqueue_step(j + 1, false)) return 1;
-                t_enq += now_us() - tq;
-                ++nmv;
+            double tq = now_us();
+            if (enq == j) {                       // the first step of the cycle, or the step behind a closed one
+                if (enqueue_step(j, j == 0, false)) return 1;
+                ++enq, ++nmv;
             }
+            if (!closed[j]) {                     // (the last step of a cycle closed itself: j + 1 < kd here)
+                if (close_mode == LAN_CLOSE_ALWAYS || (close_mode == LAN_CLOSE_AUTO && lan_expect_convergence(resids, tol))) {
+                    if (publish_step(j)) return 1;
+                } else {
+                    if (enqueue_step(j + 1, false, true)) return 1;
+                    ++enq, ++nmv;
+                }
+            }
+            t_enq += now_us() - tq;
             double a1 = 0.0, a2 = 0.0, nn = 0.0;
             tq = now_us();
             if (wait_step(j, &a1, &a2, &nn)) return 1;
@@ -837,15 +882,19 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
             amax = std::max(amax, std::max(fabs(alpha), beta));
             // invariant subspace: beta negligible RELATIVE to the scale of the tridiagonal matrix
             t_host += now_us() - tq;
-            if (res < tol || beta < 1e-14 * std::max(amax, 1e-300) || j == kd - 1) break;
+            const bool conv = res < tol || beta < 1e-14 * std::max(amax, 1e-300);
+            if (j < kd - 1 && closed[j]) ++(conv ? g_lan_close_hit : g_lan_close_miss);
+            if (j < kd - 1 && !closed[j] && conv) ++g_lan_open_conv;
+            if (conv || j == kd - 1) break;
             betas.push_back(beta);
+            resids.push_back(res);
         }
         if (ex) {
             // The step of this cycle in one launch.  No drain: the speculative step wrote row m + 1, the combination reads rows
             // 0 .. m - 1 and everything is ordered on the stream; its record, if it still arrives, fails the serial check.
-            // INVARIANT FOR CALLERS: unlike the eigen-solver path (two drains per cycle), this path RETURNS with the speculative
-            // step and the combination still in flight on `st`.  Whatever touches V, the scratch or the stage buffers next --
-            // reading the result, handing the blocks back to a pool, the next solve -- must be ordered on the same stream (the
+            // INVARIANT FOR CALLERS (the eigen-solver path below has the same one): this path RETURNS with the speculative step
+            // and the combination still in flight on `st`.  Whatever touches V, the scratch or the stage buffers next -- reading
+            // the result, handing the blocks back to a pool, the next solve -- must be ordered on the same stream (the
             // engine's pool, relay and downloads are; torch's allocator is for its current stream) or wait for it.
             if (!ex->converged && restart == max_restart) {
                 HIP_TRY(htn_stream_spin(st));
@@ -864,28 +913,36 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
             if (ex->remaining == 0.0) break;
             continue;
         }
-        HIP_TRY(htn_stream_spin(st));       // drain the speculative step before rows are reused
-        // x = sum_i y_i V_i  -> scratch row kd+1, normalised into row 0
+        // x = sum_i y_i V_i in place in row 0, then normalised: the combine launch of the exponential with the real Ritz
+        // coefficients BY VALUE -- no staging buffer, no copy, no memset, and so nothing of the host's to protect by a drain.
+        // Per element it is the sum the driver used to take (from zero, i = 0 .. k - 1 in order, the imaginary part of every
+        // coefficient exactly 0; the rows past k it re-reads have coefficient 0 and add +-0 to a sum that is never -0): same bits.
+        // No drain in front of it either: a speculative step still in flight reads rows <= k and writes row k + 1 and the
+        // scalars and record slot of its own index, in stream order BEFORE the combination; its record fails the serial check.
+        // INVARIANT FOR CALLERS, as on the exponential path: this function RETURNS with that step and the three or more kernels
+        // of the Ritz vector still in flight on `st`; the next restart cycle is enqueued straight behind them.  Whatever touches
+        // V, the scratch, Q or the stage buffers next must be ordered on the same stream or wait for it.  (Checked: HipBackend's
+        // pool, upload, download, zero and the SVD's fork are all on the context's stream and download / sync wait for it;
+        // hipFree of a grown scratch synchronises the device; torch's allocator is stream-ordered for the current stream, which
+        // is the one device.py passes.)
         const int k = (int)y.size();
-        for (int i = 0; i < k; ++i) R->h_y[i] = make_double2(y[i], 0.0);
-        HIP_TRY(hipMemcpyAsync(ycoef, R->h_y, sizeof(double2) * k, hipMemcpyHostToDevice, st));
-        double2* xrow = V + (int64_t)(kd + 1) * n;
-        HIP_TRY(hipMemsetAsync(xrow, 0, sizeof(double2) * n, st));
-        hipLaunchKernelGGL(k_axpys, dim3(grid_for(n)), dim3(256), 0, st, xrow, V, n, k, ycoef, 1.0, n);
+        KrylovCoef kc;
+        for (int i = 0; i < DOT_CHUNK; ++i) kc.c[i] = make_double2(i < k ? y[i] : 0.0, 0.0);
+        launch_krylov_combine(V, n, k, n, kc, st);
         // (frozen rows: the Ritz vector is a combination of Krylov rows that are orthogonal to Q to rounding each; projecting
         // the sum once more keeps |Q^H x| at rounding whatever the number of rows)
-        if (nf > 0) project_out(xrow);
+        if (nf > 0) project_out(V);
         else
-        hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, xrow, n, norm_partial);
-        hipLaunchKernelGGL(k_scale_by_norm, dim3(grid_for(n)), dim3(DOT_THREADS), 0, st, V, xrow, norm_partial, n,
+        hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, n, norm_partial);
+        hipLaunchKernelGGL(k_scale_by_norm, dim3(grid_for(n)), dim3(DOT_THREADS), 0, st, V, V, norm_partial, n,
                            (LanRecord*)nullptr, (const double2*)nullptr, (const double2*)nullptr, 0ull);
-        HIP_TRY(htn_stream_spin(st));      // h_y is reused by the next restart / call
         if (res < tol || beta < 1e-14 * std::max(amax, 1e-300)) break;
     }
     HIP_TRY(hipGetLastError());
     if (dbg_timers)
-        fprintf(stderr, "lanczos n=%lld: %d matvecs in %.1f us: enqueue %.1f, waiting for records %.1f, tridiagonal %.1f\n", (long long)n, nmv,
-                now_us() - t_begin, t_enq, t_wait, t_host);
+        fprintf(stderr, "lanczos n=%lld: %d matvecs in %.1f us: enqueue %.1f, waiting for records %.1f, tridiagonal %.1f; process totals: "
+                "closed steps converged %lld, not converged %lld, convergence at an open step %lld\n", (long long)n, nmv,
+                now_us() - t_begin, t_enq, t_wait, t_host, g_lan_close_hit.load(), g_lan_close_miss.load(), g_lan_open_conv.load());
     *eig_host = ex ? ex->alpha0 : theta;
     *n_matvec_host = nmv;
     *residual_host = ex ? ex->err_total : res;

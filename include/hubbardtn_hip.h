@@ -114,6 +114,10 @@ int htn_scale_inv_sqrt_z(void* dst, const void* src, const void* nrm2, int64_t n
  * basis kept in full, explicit two-pass reorthogonalisation, tridiagonal problem solved after every expansion,
  * stop when |beta_j y_j| < tol, restart from the Ritz vector at krylovdim (2 <= krylovdim <= 31).
  * V: (krylovdim + 2) * n complex128; on entry V[0:n] = start vector, on exit V[0:n] = normalised Ritz vector.
+ * The scalar results are final on return; the kernels that write V[0:n] (and possibly one speculative step that writes
+ * another row of V) may still be IN FLIGHT on `stream`: read V, free or reuse V, scratch and the stage buffers in stream
+ * order or after a synchronisation.  n_matvec counts the matvec launches enqueued (HTN_LANCZOS_CLOSE=never|always|auto in
+ * the environment decides which steps are followed by a speculative one: never the results, only this count).
  * exchange (may be NULL): called on the host after each matvec has been ENQUEUED, with the device pointer of y;
  * the multi-GPU host uses it to enqueue an RCCL all-reduce of y on the same stream (zero_y = 1 then clears y
  * before the local tiles are written).  The call synchronises the stream once per iteration (it needs
