@@ -1,0 +1,372 @@
+// Host statements of the htn::Backend methods that are not pure (htn_core.h), and of the two kernel-level entries that have
+// one (htn_krylov_expm_z, htn_qr_blocks_z): vectors downloaded, H applied through the backend's grouped_gemm, the arithmetic
+// in plain C++.  The CPU baseline library runs them; the HIP backend overrides every one with its kernels.  Nothing here
+// uses the sweep engine's types.  Host C++ (no HIP).
+// NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
+#include <math.h>
+
+#include <algorithm>
+
+#include "htn_core.h"
+#include "htn_expm.h"
+#include "htn_tridiag.h"
+
+using namespace htn;
+
+namespace {
+cplx hdot(const cplx* a, const cplx* b, int64_t n) {
+    cplx s = 0.0;
+    for (int64_t e = 0; e < n; ++e) s += std::conj(a[e]) * b[e];
+    return s;
+}
+// w -= sum_r rows[r] <rows[r], w>, twice; returns the sum of <rows[pick], w> over both passes.  Out of line, as g++ -O3 kept it
+// before the two callers shared a step: inlined into HostKrylov::extend its complex products contract to other FMAs
+__attribute__((noinline)) double hproject(const std::vector<const cplx*>& rows, cplx* w, int64_t n, int pick) {
+    double got = 0.0;
+    std::vector<cplx> c(rows.size());
+    for (int pass = 0; pass < 2; ++pass) {
+        for (size_t r = 0; r < rows.size(); ++r) c[r] = hdot(rows[r], w, n);
+        if (pick >= 0) got += c[(size_t)pick].real();
+        for (size_t r = 0; r < rows.size(); ++r)
+            for (int64_t e = 0; e < n; ++e) w[e] -= c[r] * rows[r][e];
+    }
+    return got;
+}
+
+// What lanczos_orth and krylov_expm share: host copies B of the basis rows (row 0 downloaded from the caller's V), H through
+// the device rows kd (x) and kd + 1 (y) of V, one Lanczos step with full two-pass reorthogonalisation, the combination of the
+// rows into the next start vector.  `who` prefixes the error strings.
+struct HostKrylov {
+    Backend* be;
+    const char* who;
+    const htn_gemm_launch* stages;
+    int n_stages, x_slot, y_slot;
+    cplx* Vd;
+    int64_t n;
+    int kd, zero_y;
+    htn_exchange2_fn exchange;
+    void* user;
+    size_t bytes = sizeof(cplx) * (size_t)n;
+    std::vector<cplx> B = std::vector<cplx>((size_t)(kd + 1) * n), x = std::vector<cplx>((size_t)n);
+    int n_matvec = 0;
+    cplx* row(int j) { return B.data() + (int64_t)j * n; }
+    int matvec(const cplx* v, cplx* w) {
+        cplx *xd = Vd + (int64_t)kd * n, *yd = Vd + (int64_t)(kd + 1) * n;
+        if (be->upload(xd, v, bytes)) return 1;
+        if (zero_y && be->zero(yd, bytes)) return 1;
+        for (int s = 0; s < n_stages; ++s) {
+            const void* bufs[HTN_MAX_BUFS];
+            for (int b = 0; b < HTN_MAX_BUFS; ++b) bufs[b] = stages[s].bufs[b];
+            bufs[x_slot] = xd;
+            bufs[y_slot] = yd;
+            if (stages[s].n_tiles > 0 && be->grouped_gemm(bufs, stages[s].tiles, stages[s].n_tiles, stages[s].segs)) return 1;
+        }
+        if (exchange && exchange(yd, n, user)) return set_error("%s: the exchange hook reported a failure", who);
+        return be->download(w, yd, bytes);
+    }
+    // step j: row j + 1 = H row j, orthogonalised against `frozen` and the rows 0..j -> alpha_j, beta_j (row j + 1 not yet scaled)
+    int extend(const std::vector<const cplx*>& frozen, int j, double* alpha, double* beta) {
+        cplx* w = row(j + 1);
+        if (matvec(row(j), w)) return 1;
+        ++n_matvec;
+        std::vector<const cplx*> rows = frozen;
+        for (int r = 0; r <= j; ++r) rows.push_back(row(r));
+        *alpha = hproject(rows, w, n, (int)frozen.size() + j);
+        *beta = sqrt(hdot(w, w, n).real());
+        if (!(*alpha == *alpha) || !(*beta == *beta)) return set_error("%s: NaN in the tridiagonal coefficients", who);
+        return 0;
+    }
+    void accept(int j, double beta) {                 // the step goes on: row j + 1 becomes a unit vector
+        cplx* w = row(j + 1);
+        const double inv = 1.0 / beta;
+        for (int64_t e = 0; e < n; ++e) w[e] *= inv;
+    }
+    template <class T>
+    void combine(const std::vector<T>& c) {           // x = sum_r c_r B_r
+        std::fill(x.begin(), x.end(), cplx(0.0, 0.0));
+        for (size_t r = 0; r < c.size(); ++r)
+            for (int64_t e = 0; e < n; ++e) x[(size_t)e] += c[r] * B[r * (size_t)n + (size_t)e];
+    }
+    void restart_from_x() { memcpy((void*)B.data(), x.data(), bytes); }
+    int finish() { return be->upload(Vd, B.data(), bytes) || be->sync(); }
+};
+}  // namespace
+
+int Backend::lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* Vv, int64_t n, int kd, double tol,
+                          int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, const void* Qv, int nf, double* eig,
+                          int* n_matvec, double* residual, double* matvec_ms) {
+    if (kd < 2 || nf < 0) return set_error("lanczos_orth: krylovdim >= 2 and n_frozen >= 0 required");
+    HostKrylov K{this, "lanczos_orth", stages, n_stages, x_slot, y_slot, (cplx*)Vv, n, kd, zero_y, exchange, user};
+    std::vector<cplx> Q((size_t)nf * n);
+    if (nf && download(Q.data(), Qv, K.bytes * nf)) return 1;
+    if (download(K.B.data(), K.Vd, K.bytes)) return 1;
+    auto normalise = [&](cplx* v) {
+        const double nn = hdot(v, v, n).real();
+        const double s = nn > 0.0 ? 1.0 / sqrt(nn) : 0.0;
+        for (int64_t e = 0; e < n; ++e) v[e] *= s;
+        return nn;
+    };
+    std::vector<const cplx*> qrows;
+    for (int r = 0; r < nf; ++r) qrows.push_back(Q.data() + (int64_t)r * n);
+    hproject(qrows, K.row(0), n, -1);
+    if (!(normalise(K.row(0)) > 0.0)) return set_error("lanczos_orth: the start vector lies in the span of the frozen rows");
+    double theta = 0.0, res = 0.0, alpha = 0.0, beta = 0.0, amax = 0.0;
+    std::vector<double> y;
+    for (int restart = 0; restart <= max_restart; ++restart) {
+        std::vector<double> alphas, betas;
+        for (int j = 0; j < kd; ++j) {
+            if (K.extend(qrows, j, &alpha, &beta)) return 1;
+            alphas.push_back(alpha);
+            tridiag_lowest(alphas, betas, &theta, y);
+            res = fabs(beta * y.back());
+            amax = std::max(amax, std::max(fabs(alpha), beta));
+            if (res < tol || beta < 1e-14 * std::max(amax, 1e-300) || j == kd - 1) break;
+            betas.push_back(beta);
+            K.accept(j, beta);
+        }
+        K.combine(y);
+        hproject(qrows, K.x.data(), n, -1);
+        normalise(K.x.data());
+        K.restart_from_x();
+        if (res < tol || beta < 1e-14 * std::max(amax, 1e-300)) break;
+    }
+    if (K.finish()) return 1;
+    *eig = theta;
+    *n_matvec = K.n_matvec;
+    *residual = res;
+    if (matvec_ms) *matvec_ms = 0.0;
+    return 0;
+}
+
+// x = exp(-i dt H) x0, host statement (htn_core.h): the Lanczos basis with full two-pass reorthogonalisation on host copies of
+// the vectors, H through grouped_gemm, the stopping / sub-stepping decisions of htn_expm::Expm -- the ones the device driver takes
+int Backend::krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* Vv, int64_t n, int kd, double dt_re,
+                         double dt_im, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user, double* growth,
+                         double* alpha0, int* n_matvec, double* err, double* matvec_ms) {
+    if (kd < 2 || kd > 31) return set_error("krylov_expm: krylovdim must be in 2..31");
+    if (!Vv || n <= 0) return set_error("krylov_expm: bad arguments");
+    HostKrylov K{this, "krylov_expm", stages, n_stages, x_slot, y_slot, (cplx*)Vv, n, kd, zero_y, exchange, user};
+    if (download(K.B.data(), K.Vd, K.bytes)) return 1;
+    {
+        const double nn = hdot(K.row(0), K.row(0), n).real();
+        if (!(nn > 0.0)) return set_error("krylov_expm: the start vector is zero or not finite");
+        const double sc = 1.0 / sqrt(nn);
+        for (int64_t e = 0; e < n; ++e) K.B[(size_t)e] *= sc;
+    }
+    htn_expm::Expm ex;
+    ex.dt_re = dt_re, ex.dt_im = dt_im, ex.tol = tol;
+    const std::vector<const cplx*> none;
+    for (int restart = 0;; ++restart) {
+        ex.begin_cycle();
+        for (int j = 0; j < kd; ++j) {
+            double alpha, beta;
+            if (K.extend(none, j, &alpha, &beta)) return 1;
+            bool bad = false;
+            const bool stop = ex.step(alpha, beta, kd, &bad);
+            if (bad) return set_error("krylov_expm: the QL iteration of the tridiagonal matrix did not converge");
+            if (stop) break;
+            K.accept(j, beta);
+        }
+        if (!ex.converged && restart >= max_restart)
+            return set_error("krylov_expm: not converged after %d restart(s) of krylovdim %d: fraction %.3e of dt remains (estimate %.3e, tol %.3e)",
+                             std::max(max_restart, 0), kd, ex.remaining, ex.est, tol);
+        if (!ex.finish()) return set_error("krylov_expm: no fraction of the step down to 2^-60 meets the tolerance");
+        K.combine(ex.c);
+        K.restart_from_x();
+        if (ex.remaining == 0.0) break;
+    }
+    if (K.finish()) return 1;
+    *growth = ex.growth;
+    *alpha0 = ex.alpha0;
+    *n_matvec = K.n_matvec;
+    *err = ex.err_total;
+    if (matvec_ms) *matvec_ms = 0.0;
+    return 0;
+}
+
+int Backend::orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept) {
+    std::vector<cplx> h((size_t)nvec * n);
+    if (nvec && download(h.data(), P, sizeof(cplx) * h.size())) return 1;
+    std::vector<const cplx*> rows;
+    int k = 0;
+    for (int r = 0; r < nvec; ++r) {
+        cplx* dst = h.data() + (int64_t)k * n;
+        if (r != k) memcpy((void*)dst, h.data() + (int64_t)r * n, sizeof(cplx) * (size_t)n);
+        const double n0 = hdot(dst, dst, n).real();
+        hproject(rows, dst, n, -1);
+        const double n1 = hdot(dst, dst, n).real();
+        if (!(n0 > 0.0) || !(n1 > drop_tol * drop_tol * n0)) continue;
+        const double sc = 1.0 / sqrt(n1);
+        for (int64_t e = 0; e < n; ++e) dst[e] *= sc;
+        rows.push_back(dst);
+        ++k;
+    }
+    if (k && (upload(P, h.data(), sizeof(cplx) * (size_t)k * n) || sync())) return 1;
+    *kept = k;
+    return 0;
+}
+
+// Householder QR of the blocks on host memory (conventions of htn_qr_blocks_z: R / L diagonal real and non-negative, a column
+// whose remainder is below 1e-13 of its norm gets an exact zero there and no reflector -- Q stays orthonormal by construction)
+void htn::qr_blocks_host(cplx* A, cplx* Rb, const htn_qr_block* desc, int n_blocks) {
+    std::vector<cplx> M, Q, V;
+    std::vector<double> tau, cn;
+    std::vector<cplx> ph;
+    for (int b = 0; b < n_blocks; ++b) {
+        const htn_qr_block& D = desc[b];
+        const int64_t m = D.m, n = D.n;
+        if (m <= 0 || n <= 0) continue;
+        M.assign((size_t)(m * n), cplx(0.0, 0.0));
+        V.assign((size_t)(m * n), cplx(0.0, 0.0));
+        tau.assign((size_t)n, 0.0);
+        cn.assign((size_t)n, 0.0);
+        ph.assign((size_t)n, cplx(1.0, 0.0));
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = 0; i < m; ++i) {
+                M[(size_t)(i + j * m)] = D.trans ? std::conj(A[D.offset + j + i * D.ld]) : A[D.offset + i + j * D.ld];
+                cn[(size_t)j] += std::norm(M[(size_t)(i + j * m)]);
+            }
+        for (int64_t k = 0; k < n; ++k) {
+            double n2 = 0.0;
+            for (int64_t i = k; i < m; ++i) n2 += std::norm(M[(size_t)(i + k * m)]);
+            const double nr = sqrt(n2);
+            if (!(nr > 1e-13 * sqrt(cn[(size_t)k]))) {
+                for (int64_t i = k; i < m; ++i) M[(size_t)(i + k * m)] = cplx(0.0, 0.0);
+                continue;
+            }
+            const cplx x0 = M[(size_t)(k + k * m)];
+            const cplx p = std::abs(x0) > 0.0 ? x0 / std::abs(x0) : cplx(1.0, 0.0);
+            const cplx beta = -p * nr;
+            double vn2 = 0.0;
+            for (int64_t i = k; i < m; ++i) {
+                V[(size_t)(i + k * m)] = M[(size_t)(i + k * m)] - (i == k ? beta : cplx(0.0, 0.0));
+                vn2 += std::norm(V[(size_t)(i + k * m)]);
+            }
+            tau[(size_t)k] = 2.0 / vn2;
+            ph[(size_t)k] = -p;
+            for (int64_t j = k + 1; j < n; ++j) {
+                cplx w(0.0, 0.0);
+                for (int64_t i = k; i < m; ++i) w += std::conj(V[(size_t)(i + k * m)]) * M[(size_t)(i + j * m)];
+                w *= tau[(size_t)k];
+                for (int64_t i = k; i < m; ++i) M[(size_t)(i + j * m)] -= V[(size_t)(i + k * m)] * w;
+            }
+            M[(size_t)(k + k * m)] = beta;
+            for (int64_t i = k + 1; i < m; ++i) M[(size_t)(i + k * m)] = cplx(0.0, 0.0);
+        }
+        Q.assign((size_t)(m * n), cplx(0.0, 0.0));
+        for (int64_t j = 0; j < n; ++j) Q[(size_t)(j + j * m)] = cplx(1.0, 0.0);
+        for (int64_t k = n - 1; k >= 0; --k) {
+            if (tau[(size_t)k] == 0.0) continue;
+            for (int64_t j = 0; j < n; ++j) {
+                cplx w(0.0, 0.0);
+                for (int64_t i = k; i < m; ++i) w += std::conj(V[(size_t)(i + k * m)]) * Q[(size_t)(i + j * m)];
+                w *= tau[(size_t)k];
+                for (int64_t i = k; i < m; ++i) Q[(size_t)(i + j * m)] -= V[(size_t)(i + k * m)] * w;
+            }
+        }
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = 0; i < m; ++i) {
+                const cplx q = Q[(size_t)(i + j * m)] * ph[(size_t)j];
+                if (D.trans) A[D.offset + j + i * D.ld] = std::conj(q);
+                else A[D.offset + i + j * D.ld] = q;
+            }
+        for (int64_t j = 0; j < n; ++j)
+            for (int64_t i = 0; i < n; ++i) {
+                cplx r = i <= j ? M[(size_t)(i + j * m)] * std::conj(ph[(size_t)i]) : cplx(0.0, 0.0);
+                if (i == j) r = cplx(r.real(), 0.0);
+                if (D.trans) Rb[D.r_offset + j + i * D.ldr] = std::conj(r);
+                else Rb[D.r_offset + i + j * D.ldr] = r;
+            }
+    }
+}
+
+int Backend::qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks) {
+    (void)desc_dev;
+    if (n_blocks <= 0) return 0;
+    if (!desc_host) return set_error("qr_blocks: the host copy of the descriptors is required");
+    int64_t a0 = INT64_MAX, a1 = 0, r0 = INT64_MAX, r1 = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        const htn_qr_block& D = desc_host[b];
+        const int64_t vr = D.trans ? D.n : D.m, vc = D.trans ? D.m : D.n;
+        a0 = std::min(a0, D.offset), a1 = std::max(a1, D.offset + (vc - 1) * D.ld + vr);
+        r0 = std::min(r0, D.r_offset), r1 = std::max(r1, D.r_offset + (int64_t)(D.n - 1) * D.ldr + D.n);
+    }
+    std::vector<cplx> ha((size_t)(a1 - a0)), hr((size_t)(r1 - r0));
+    if (download(ha.data(), (cplx*)A + a0, sizeof(cplx) * ha.size()) || download(hr.data(), (cplx*)R + r0, sizeof(cplx) * hr.size()))
+        return 1;
+    std::vector<htn_qr_block> d(desc_host, desc_host + n_blocks);
+    for (auto& D : d) D.offset -= a0, D.r_offset -= r0;
+    qr_blocks_host(ha.data(), hr.data(), d.data(), n_blocks);
+    if (upload((cplx*)A + a0, ha.data(), sizeof(cplx) * ha.size()) || upload((cplx*)R + r0, hr.data(), sizeof(cplx) * hr.size())) return 1;
+    return sync();
+}
+
+int Backend::block_trdots(const void* A, const void* B, const htn_trdot_item* items_dev, const htn_trdot_item* items, int n_items,
+                          void* out, int n_out) {
+    (void)items_dev;
+    if (n_out <= 0) return 0;
+    if (n_items > 0 && !items) return set_error("block_trdots: the host copy of the items is required");
+    int64_t a0 = INT64_MAX, a1 = 0, b0 = INT64_MAX, b1 = 0;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_trdot_item& it = items[q];
+        if (it.rows <= 0 || it.cols <= 0) continue;
+        a0 = std::min(a0, it.a_off), a1 = std::max(a1, it.a_off + (int64_t)(it.cols - 1) * it.lda + it.rows);
+        b0 = std::min(b0, it.b_off), b1 = std::max(b1, it.b_off + (int64_t)(it.rows - 1) * it.ldb + it.cols);
+    }
+    std::vector<cplx> ha((size_t)std::max<int64_t>(a1 - a0, 0)), hb((size_t)std::max<int64_t>(b1 - b0, 0)), res((size_t)n_out, cplx(0.0, 0.0));
+    if (!ha.empty() && download(ha.data(), (const cplx*)A + a0, sizeof(cplx) * ha.size())) return 1;
+    if (!hb.empty() && download(hb.data(), (const cplx*)B + b0, sizeof(cplx) * hb.size())) return 1;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_trdot_item& it = items[q];
+        if (it.out < 0 || it.out >= n_out) return set_error("block_trdots: item %d adds to result %d of %d", q, it.out, n_out);
+        if (it.rows <= 0 || it.cols <= 0) continue;
+        const cplx *a = ha.data() + (it.a_off - a0), *b = hb.data() + (it.b_off - b0);
+        double sr = 0.0, si = 0.0;                       // A[r, c] * B[c, r], no conjugation
+        for (int64_t c = 0; c < it.cols; ++c)
+            for (int64_t r = 0; r < it.rows; ++r) {
+                const cplx x = a[r + c * it.lda], y = b[c + r * it.ldb];
+                sr += x.real() * y.real() - x.imag() * y.imag();
+                si += x.real() * y.imag() + x.imag() * y.real();
+            }
+        res[(size_t)it.out] += cplx(it.w_re * sr - it.w_im * si, it.w_re * si + it.w_im * sr);
+    }
+    return upload(out, res.data(), sizeof(cplx) * res.size());
+}
+
+// ---- the kernel-level entries that have a host-memory statement: what the CPU baseline library exports ------------------
+extern "C" {
+
+// Host-memory statement of the kernel-level entry: what the CPU baseline library exports (V and the buffers of the stages are
+// host pointers, the stages run through that library's grouped GEMM, scratch and stream are not used).  Weak: in
+// libhubbardtn_hip.so the definition of htn_krylov.hip (device pointers, the gfx950 kernels) takes its place at link time.
+__attribute__((weak)) int htn_krylov_expm_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot, void* V, int64_t n,
+                                            int32_t krylovdim, double dt_re, double dt_im, double tol, int32_t max_restart, void* scratch,
+                                            int32_t zero_y, htn_exchange2_fn exchange, void* user, double* growth_host, double* alpha0_host,
+                                            int32_t* n_matvec_host, double* err_host, double* matvec_ms_host, void* stream) {
+    (void)scratch, (void)stream;
+    if (!stages || !V || !growth_host || !alpha0_host || !n_matvec_host || !err_host) return set_error("htn_krylov_expm_z: bad arguments");
+    std::unique_ptr<Backend> be(make_backend(HTN_BACKEND_CPU, 0, nullptr));
+    if (!be) return 1;
+    int nmv = 0;
+    const int rc = be->krylov_expm(stages, n_stages, x_slot, y_slot, V, n, krylovdim, dt_re, dt_im, tol, max_restart, zero_y, exchange, user,
+                                   growth_host, alpha0_host, &nmv, err_host, matvec_ms_host);
+    *n_matvec_host = nmv;
+    return rc;
+}
+
+// Host-memory statement of the kernel-level entry (Householder reflections): what the CPU baseline library exports.  Weak: in
+// libhubbardtn_hip.so the definition of htn_qr.hip (device pointers, the gfx950 kernel) takes its place at link time.
+__attribute__((weak)) int htn_qr_blocks_z(void* A, void* Rbuf, const htn_qr_block* desc, const htn_qr_block* desc_host, int32_t n_blocks,
+                                          void* stream) {
+    (void)stream;
+    if (n_blocks <= 0) return 0;
+    if (!A || !Rbuf || (!desc && !desc_host)) return set_error("htn_qr_blocks_z: bad arguments");
+    const htn_qr_block* d = desc_host ? desc_host : desc;
+    for (int b = 0; b < n_blocks; ++b)
+        if (d[b].n < 1 || d[b].m < d[b].n || d[b].ldr < d[b].n || d[b].ld < (d[b].trans ? d[b].n : d[b].m))
+            return set_error("htn_qr_blocks_z: block %d: m = %d, n = %d, ld = %d, ldr = %d (need m >= n >= 1)", b, d[b].m, d[b].n, d[b].ld, d[b].ldr);
+    qr_blocks_host((cplx*)A, (cplx*)Rbuf, d, n_blocks);
+    return 0;
+}
+
+}  // extern "C"

@@ -328,14 +328,14 @@ struct Backend {
                         int krylovdim, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
                         double* eig, int* n_matvec, double* residual, double* matvec_ms) = 0;
     // Lowest eigenpair of P H P, P = 1 - Q Q^H, for n_frozen orthonormal device rows Q of length n (start vector projected
-    // first; V as for lanczos).  NOT pure: the default (htn_engine.cpp) is a plain host statement of the method -- vectors
+    // first; V as for lanczos).  NOT pure: the default (htn_backend_host.cpp) is a plain host statement of the method -- vectors
     // downloaded, H applied through grouped_gemm, full reorthogonalisation against Q and the basis in two passes, the stopping
     // rule of lanczos -- which the CPU baseline library inherits; the HIP backend overrides it with htn_lanczos_orth_z.
     virtual int lanczos_orth(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n,
                              int krylovdim, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
                              const void* Q, int n_frozen, double* eig, int* n_matvec, double* residual, double* matvec_ms);
     // x = exp(-i dt H) x0 on the device row V[0] (htn_krylov_expm_z in the header: outputs, stopping and sub-stepping rule).
-    // NOT pure: the default (htn_engine.cpp) is a plain host statement of the method -- vectors downloaded, H applied through
+    // NOT pure: the default (htn_backend_host.cpp) is a plain host statement of the method -- vectors downloaded, H applied through
     // grouped_gemm, full two-pass reorthogonalisation, the decisions of htn_expm::Expm -- which the CPU baseline library
     // inherits; the HIP backend overrides it with htn_krylov_expm_z.
     virtual int krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim,
@@ -345,11 +345,11 @@ struct Backend {
     // norm is dropped and the rows behind it move up.  -> *kept orthonormal rows.  Default: on the host.
     virtual int orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept);
     // Unpivoted QR / LQ of strided blocks in place with the orthonormal factor formed (htn_qr_blocks_z in the header).  Default
-    // (htn_engine.cpp): download, Householder reflections on the host, upload -- what the CPU baseline library runs; the HIP
+    // (htn_backend_host.cpp): download, Householder reflections on the host, upload -- what the CPU baseline library runs; the HIP
     // backend overrides it with the kernel.
     virtual int qr_blocks(void* A, void* R, const htn_qr_block* desc_dev, const htn_qr_block* desc_host, int n_blocks);
     // out[o] = sum of w * sum_{r,c} A[r, c] B[c, r] over the items of result o (htn_block_trdots_z in the header); every one of the
-    // n_out results is written.  Default (htn_engine.cpp): download the ranges the items touch, sum on the host in list order,
+    // n_out results is written.  Default (htn_backend_host.cpp): download the ranges the items touch, sum on the host in list order,
     // upload -- what the CPU baseline library runs; the HIP backend overrides it with the kernel.
     virtual int block_trdots(const void* A, const void* B, const htn_trdot_item* items_dev, const htn_trdot_item* items_host,
                              int n_items, void* out, int n_out);
@@ -365,6 +365,8 @@ struct Backend {
     virtual int allreduce(void* y, int64_t n) { return 1; }
     bool timing = false;
 };
+
+Backend* make_backend(int backend, int device, void* stream);       // one per library (htn_backend_hip.hip / cpu)
 
 // Householder QR / LQ of the blocks on HOST memory, conventions of htn_qr_blocks_z
 void qr_blocks_host(cplx* A, cplx* R, const htn_qr_block* desc, int n_blocks);

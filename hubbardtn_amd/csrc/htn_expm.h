@@ -1,6 +1,6 @@
 // Host side of the Krylov exponential x = exp(-i dt H) x0 (htn_krylov_expm_z and htn::Backend::krylov_expm): what is done with
 // the tridiagonal coefficients (alpha_j, beta_j) of an orthonormal Lanczos basis.  Plain C++, header only: the device driver
-// (htn_krylov.hip) and the host statement of the method (htn_engine.cpp) take the SAME decisions from the same numbers.
+// (htn_krylov.hip) and the host statement of the method (htn_backend_host.cpp) take the SAME decisions from the same numbers.
 //
 //   after step m:   T_m = tridiag(alpha_0..alpha_{m-1}; beta_0..beta_{m-2}) is diagonalised completely (implicit QL, m <= 31),
 //                   c = exp(-i dt T_m) e_1,   est = beta_m |dt| |c_m|   (Saad's a-posteriori estimate, SIAM J. Numer. Anal. 29, 1992)

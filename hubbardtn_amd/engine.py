@@ -1,4 +1,4 @@
-"""Thin Python face of the C++ sweep engine (hubbardtn_amd/csrc/htn_engine.cpp behind include/hubbardtn_hip.h).
+"""Thin Python face of the C++ sweep engine (hubbardtn_amd/csrc/htn_engine.cpp and the files around it, behind include/hubbardtn_hip.h).
 
 Everything below `find_groundstate(psi0, H, alg)` (src/HubbardFunctions.jl:1010) -- sector layouts, recoupling
 coefficients, task lists, theta formation, Lanczos, per-sector SVD, the global truncation rule, write-back,

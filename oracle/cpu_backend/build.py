@@ -1,8 +1,9 @@
 """Builds oracle/cpu_backend/libhubbardtn_cpu.so: the CPU baseline / checker behind the same C ABI as the product
 (see htn_backend_cpu.cpp).  g++ + OpenMP; the planner and sweep-driver sources are the product's own
-(hubbardtn_amd/csrc/htn_plan.cpp, htn_engine.cpp), only the kernels differ."""
+(the host sources of hubbardtn_amd/csrc: htn_plan.cpp, htn_engine.cpp and the files it includes), only the kernels differ."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -10,6 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "hubbardtn_amd", "csrc")
+# htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
+# unit on purpose (bit-identical host arithmetic, see its head).  Do not list those files here: every symbol would be defined twice.
 SRCS = [os.path.join(CSRC, "htn_plan.cpp"), os.path.join(CSRC, "htn_engine.cpp"), os.path.join(HERE, "htn_backend_cpu.cpp")]
 LIB = os.path.join(HERE, "libhubbardtn_cpu.so")
 
@@ -18,7 +21,8 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = SRCS + [os.path.join(CSRC, "htn_core.h"), os.path.join(ROOT, "include", "hubbardtn_hip.h")]
+    # (every header, and every .cpp: htn_engine.cpp includes the files the engine is split into)
+    deps = SRCS + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.cpp")) + [os.path.join(ROOT, "include", "hubbardtn_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

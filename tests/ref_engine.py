@@ -1,4 +1,4 @@
-"""TEST STATEMENT of the sweep driver in Python (the product's driver is C++: hubbardtn_amd/csrc/htn_engine.cpp),
+"""TEST STATEMENT of the sweep driver in Python (the product's driver is C++: hubbardtn_amd/csrc/htn_engine.cpp, htn_site.cpp),
 executed by the CPU suite on the numpy emulator of the kernel-level ABI (tests/emul.py).
 
 Two-site DMRG sweep engine (finite chain) on the device primitives of hubbardtn_hip.h.

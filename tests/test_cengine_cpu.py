@@ -1,4 +1,4 @@
-"""The product's C++ planner + sweep driver (hubbardtn_amd/csrc/htn_plan.cpp, htn_engine.cpp) executed WITHOUT a GPU on
+"""The product's C++ planner + sweep driver (hubbardtn_amd/csrc/htn_plan.cpp, htn_engine.cpp and the files around it) executed WITHOUT a GPU on
 the CPU baseline backend (oracle/cpu_backend, same C ABI): byte-identity with the Python test statement of the planner,
 parity with the numpy oracle and exact diagonalisation, observables, the on-disk formats and the C-ABI-only drive of a
 whole sweep.  (The `-m gpu` suite runs the same engine on the HIP kernels.)"""

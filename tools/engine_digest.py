@@ -1,0 +1,151 @@
+"""Bit-level fingerprint of the sweep engine, for refactors that must not change what it computes.
+
+    python tools/engine_digest.py --backend cpu [--lib path/to/libhubbardtn_cpu.so]
+    python tools/engine_digest.py --backend hip [--lib path/to/libhubbardtn_hip.so]
+
+Runs fixed-seed scenarios on a small chain through the Python face of the C ABI and prints one line per scenario: the first 32 hex
+digits of a sha256 over the sweep energies, the per-update energy / discarded weight / matvec, Jacobi-sweep, chi, multiplet, tile
+and segment counts, every bond's spectrum and every exported site tensor, then the plan cache's (hits, misses).  Two builds of
+the library compute the same thing exactly when all lines agree.  Without --lib the library of this tree is used (built if
+needed); with --lib nothing is built.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from hubbardtn_amd import abi, engine, idmrg, models, mps  # noqa: E402
+
+
+class Ops:
+    """context provider around one library file (what tests/cpu_ops.py and hubbardtn_amd/device.py are for the default paths)"""
+
+    def __init__(self, backend, path):
+        if backend == "cpu":
+            if path is None:
+                from oracle.cpu_backend import build as cpu_build
+                path = cpu_build.build_library(verbose=False)
+            self.lib = C.CDLL(path)
+            abi.declare_engine(self.lib)
+            self.lib.htn_cpu_set_threads(4)
+            kind = abi.BACKEND_CPU
+        else:
+            self.lib = abi.load_library(path)
+            name, cus = C.create_string_buffer(256), C.c_int(0)
+            abi.check(self.lib, self.lib.htn_device_init(0, name, C.byref(cus)), "htn_device_init")
+            kind = abi.BACKEND_HIP
+        h = C.c_void_p()
+        abi.check(self.lib, self.lib.htn_ctx_create(kind, 0, None, C.byref(h)), "htn_ctx_create")
+        self.ctx = h
+
+    def __del__(self):
+        h, self.ctx = getattr(self, "ctx", None), None
+        if h:
+            self.lib.htn_ctx_destroy(h)
+
+
+COUNTS = ("n_matvec", "jacobi_sweeps", "chi_full", "multiplets", "n_tiles", "n_segs")
+
+
+class Digest:
+    def __init__(self):
+        self.h = hashlib.sha256()
+
+    def floats(self, x):
+        self.h.update(np.ascontiguousarray(x, dtype=np.complex128 if np.iscomplexobj(x) else np.float64).tobytes())
+
+    def ints(self, x):
+        self.h.update(np.ascontiguousarray(x, dtype=np.int64).tobytes())
+
+    def stats(self, stats):
+        for s in stats:
+            self.floats([s.energy, s.trunc_weight])
+            self.ints([getattr(s, k) for k in COUNTS])
+
+    def state(self, eng):
+        for b in range(eng.L + 1):
+            for sec, vals in sorted(eng.spectrum(b).items()):
+                self.ints(sec)
+                self.floats(vals)
+        for i in range(eng.L):
+            for key, blk in sorted(eng.download_site(i).items()):
+                self.ints([key[0][0], key[0][1], key[1], key[2][0], key[2][1]])
+                self.floats(np.asfortranarray(blk).reshape(-1, order="F"))
+
+    def hex(self):
+        return self.h.hexdigest()[:32]
+
+
+def report(name, d, eng):
+    print(f"{name:<44s}| {d.hex()} {eng._cache_stats()}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--backend", choices=("cpu", "hip"), required=True)
+    ap.add_argument("--lib", default=None, help="library file to fingerprint (default: this tree's)")
+    a = ap.parse_args()
+    ops = Ops(a.backend, a.lib)
+    L, target = 8, (8, 0)
+    sim = models.OB_Sim([1.0], [4.0])
+    H = models.hamiltonian(sim, L)
+
+    def fresh(seed):
+        bonds, tens = mps.random_mps(L, target, 6, seed=seed)
+        return engine.DMRG2(ops, H, bonds, tens, chi_full=64, krylovdim=20)
+
+    gs = fresh(11)
+    d = Digest()
+    d.floats([gs.sweep(), gs.sweep()])
+    d.stats(gs.stats)
+    d.state(gs)
+    report("two two-site sweeps, L=8 chi=64", d, gs)
+
+    d, n0 = Digest(), len(gs.stats)
+    d.floats([gs.sweep1()])
+    d.stats(gs.stats[n0:])
+    d.state(gs)
+    report("one one-site sweep after them", d, gs)
+
+    ex = fresh(23)
+    ex.set_orthogonal([gs])
+    d = Digest()
+    d.floats([ex.sweep()])
+    d.stats(ex.stats)
+    d.ints([ex.dropped_projectors()])
+    d.state(ex)
+    report("one excited-state sweep, one attached state", d, ex)
+    ex.set_orthogonal([])
+
+    res = idmrg.idmrg2(ops, sim, chi_full=40, maxiter=3, tol=1e-12, seed=77, warm_start=True, driver="native")
+    d = Digest()
+    d.floats([x for pair in res.history for x in pair])
+    d.ints([res.iterations, res.sweeps])
+    d.state(res.engine)
+    report("three IDMRG2 steps, warm start (native)", d, res.engine)
+
+    ev = gs.copy()
+    d = Digest()
+    for dt in (0.05, -0.05j):
+        d.floats([ev.tdvp_sweep(dt), ev.log_norm])
+    d.stats(ev.stats)
+    d.state(ev)
+    report("two TDVP2 steps, dt real then imaginary", d, ev)
+
+    d = Digest()
+    Cm, nrm = ev.correlator_channel("n", "id", "n", "n")
+    d.floats(Cm.reshape(-1))
+    d.floats([nrm])
+    report("one correlator channel (n, id, n)", d, ev)
+
+
+if __name__ == "__main__":
+    main()
