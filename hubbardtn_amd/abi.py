@@ -44,6 +44,9 @@ TRDOT_DT = np.dtype([("a_off", "<i8"), ("b_off", "<i8"), ("rows", "<i4"), ("cols
                      ("out", "<i4"), ("pad", "<i4", (3,)), ("w_re", "<f8"), ("w_im", "<f8")], align=False)      # htn_trdot_item
 TRDOT_SLOTS = 16                                   # HTN_TRDOT_SLOTS
 assert TRDOT_DT.itemsize == 64
+PLACE_DT = np.dtype([("dst_off", "<i8"), ("src_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("ldd", "<i4"), ("lds", "<i4"),
+                     ("coef", "<f8"), ("pad", "<i4", (6,))], align=False)                                          # htn_place_item
+assert PLACE_DT.itemsize == 64
 
 # ---- bond-update / sweep level (ABI 2) ----
 SYM_SU2_U1, SYM_U1_U1, SYM_SU2 = 0, 1, 2
@@ -123,7 +126,7 @@ assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(Idmr
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
            "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z",
-           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z"]
+           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z", "htn_block_place_z"]
 # entry points shared by libhubbardtn_hip.so and the CPU baseline library (oracle/cpu_backend)
 ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_ctx_set_timing", "htn_comm_unique_id",
                   "htn_ctx_set_comm", "htn_ctx_set_exchange", "htn_mpo_create", "htn_mpo_destroy", "htn_mps_create",
@@ -135,7 +138,8 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_mps_set_orthogonal", "htn_mps_orthogonal_count", "htn_mps_overlap",
                   "htn_site_update", "htn_dmrg1_sweep", "htn_mps_centre", "htn_mps_site_theta_size", "htn_heff1_apply",
                   "htn_qr_blocks_z", "htn_mps_correlator",
-                  "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo"]
+                  "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo",
+                  "htn_mps_apply_op", "htn_mps_transition"]
 
 
 class GemmLaunch(C.Structure):
@@ -189,6 +193,7 @@ def load_library(path: str | None = None):
     lib.htn_trdots_scratch_elems.restype = i64
     lib.htn_block_trdots_z.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
     lib.htn_krylov_combine_z.argtypes = [vp, i64, i32, vp, i64, vp]
+    lib.htn_block_place_z.argtypes = [vp, vp, vp, i32, vp]
     declare_engine(lib)
     for name in EXPORTS + ENGINE_EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
@@ -267,6 +272,8 @@ def declare_engine(lib):
     lib.htn_site_evolve.argtypes = [vp, i32, f64, f64, C.POINTER(SweepOpts), vp]
     lib.htn_tdvp2_sweep.argtypes = [vp, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
     lib.htn_mps_set_mpo.argtypes = [vp, vp]
+    lib.htn_mps_apply_op.argtypes = [vp, i32, C.POINTER(SiteOp), C.POINTER(vp), C.POINTER(f64)]
+    lib.htn_mps_transition.argtypes = [vp, C.POINTER(SiteOp), vp, vp]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

@@ -618,6 +618,85 @@ def momentum_distribution(psi, q):
     return np.real(structure_factor(psi, "hop", q, connected=False)) / 2.0
 
 
+# ---- local operators on a finite MPS: G(x, t) and spectral functions ------------------------------------------------
+def apply_operator(psi, name, site):
+    """a new FiniteMPS holding O_site |psi> for the site operator `name` of the state's symmetry ("c", "c+" = "cdag", "n", "S";
+    spinful mode "c_up", "c+_up", ...; or an abi.SiteOp).  psi (centre on site 0, as after a sweep) is copied, the copy's centre
+    is carried to `site` without optimisation and the operator applied there on the device (engine.DMRG2.apply_op); psi itself
+    is untouched.  The result is not normalised: <O_x psi|O_y psi> = sum over the operator's components of <psi|O+_xq O_yq|psi>,
+    so for "c" the overlap matrix of the applied states is correlation_function(psi, "hop").  In the SU(2) modes psi must have
+    total spin 0 unless the operator is a scalar."""
+    if isinstance(psi, InfiniteMPS):
+        raise NotImplementedError("apply_operator needs a chain length: operators are applied to a finite chain "
+                                  "(pass L= / use a FiniteMPS), not to an InfiniteMPS")
+    if not 0 <= int(site) < psi.L:
+        raise ValueError(f"apply_operator: site {site} out of range (the chain has {psi.L} sites)")
+    work = psi.engine.copy()
+    work.move_centre(int(site))
+    return FiniteMPS(work.apply_op(int(site), name), psi.L)
+
+
+def greens_function(psi0, H, times, alg: TDVP2, op="c+", site=None):
+    """C[t, x] = exp(+i E0 t) <O_x psi0| exp(-i H t) O_site psi0> for all sites x and the increasing list `times` (the first entry
+    is the time of the applied state itself, normally 0), E0 = <psi0|H|psi0>, site = L // 2 by default.  One tdvp_sweep and one
+    `transition` pass per interval.  -> {"times", "C": [len(times), L], "E0", "trunc_weight", "site"}.
+    The overlaps carry the sum over the components of the operator's multiplet (apply_operator), e.g. both spins for "c+" in
+    the SU(2) modes.  The factor -i, the step function and the combination of the particle part (op = "c+") with the hole part
+    (op = "c", evolved with exp(+i H t): conjugate the result) into the retarded function are left to the caller:
+    G^R(x, t) = -i theta(t) (C_particle(t, x) + conj(C_hole(t, x))).  The evolved state is renormalised after every truncation
+    (TDVP2 of this library), so a truncating trscheme shows up in trunc_weight, not as a loss of norm."""
+    if isinstance(psi0, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
+        raise NotImplementedError("greens_function needs a chain length: it is measured on a finite chain, not on an InfiniteMPS")
+    L = psi0.L
+    site = L // 2 if site is None else int(site)
+    times = [float(t) for t in times]
+    phi = apply_operator(psi0, op, site)
+    phi.engine.move_centre(0)
+    eng = _tdvp_setup(phi, H, alg)
+    ref = psi0.engine.copy()            # (bond_energies moves the centre through the chain: not on the caller's state)
+    if H is not None and H is not ref.mpo and H is not ref.cmpo:
+        ref.set_mpo(H)
+    E0, _ = ref.bond_energies()
+    Cm = np.zeros((len(times), L), dtype=np.complex128)
+    tw = np.zeros(len(times))
+    Cm[0] = psi0.engine.transition(op, eng)
+    for k in range(1, len(times)):
+        k0 = len(eng.stats)
+        eng.tdvp_sweep(times[k] - times[k - 1])
+        tw[k] = float(sum(s.trunc_weight for s in eng.stats[k0:]))
+        Cm[k] = np.exp(1j * E0 * (times[k] - times[0])) * psi0.engine.transition(op, eng)
+    return {"times": np.array(times), "C": Cm, "E0": E0, "trunc_weight": tw, "site": site}
+
+
+def spectral_function(res, q, omegas, eta):
+    """A(q, omega) = -Im G(q, omega) / pi from a greens_function result, on the host: for t >= 0
+    G(q, omega) = -i sum_x exp(-i q (x - site)) int dt exp(i omega t) W(t) C[t, x], with the Gaussian window
+    W(t) = exp(-(eta t)^2 / 2) (a broadening of width eta in omega) and the trapezoidal rule over res["times"].  q (radians per
+    site) and omegas are scalars or arrays -> array [len(q), len(omegas)] (scalars are squeezed out).  omega is measured from
+    E0: the particle part (op = "c+") has its weight at omega = E_n(N+1) - E0.  As for momentum_distribution, an open chain has
+    no momentum eigenstates: this is the Fourier transform in the distance from `site`, not a momentum-resolved quantity of a
+    translation-invariant system, and it is not normalised over a q grid."""
+    t = np.asarray(res["times"], dtype=float) - float(res["times"][0])
+    Cm = np.asarray(res["C"])
+    L = Cm.shape[1]
+    qs, ws = np.atleast_1d(np.asarray(q, dtype=float)), np.atleast_1d(np.asarray(omegas, dtype=float))
+    ph = np.exp(-1j * qs[:, None] * (np.arange(L) - res["site"])[None, :])        # [q, x]
+    Cq = ph @ Cm.T                                                                # [q, t]
+    wt = np.zeros_like(t)                                                         # trapezoidal weights
+    if len(t) > 1:
+        dt = np.diff(t)
+        wt[:-1] += 0.5 * dt
+        wt[1:] += 0.5 * dt
+    kern = np.exp(1j * ws[:, None] * t[None, :]) * (wt * np.exp(-0.5 * (float(eta) * t) ** 2))[None, :]      # [w, t]
+    G = -1j * Cq @ kern.T                                                         # [q, w]
+    A = -G.imag / np.pi
+    if not np.ndim(q):
+        A = A[0]
+    if not np.ndim(omegas):
+        A = A[..., 0]
+    return A
+
+
 def TruncState(simul: Simulation, trunc_dim: int, trunc_scheme: int = 0, L: int | None = None, polish: str = "twosite", **kw):
     """truncated approximation of the ground state at bond dimension `trunc_dim` (TensorKit dim units), src:1351-1367.
     trunc_scheme 1 = SvdCut (truncate by SVD only); 0 = VUMPSSvdCut (truncate, then re-optimise variationally at

@@ -321,6 +321,10 @@ struct HipBackend : htn::Backend {
         }
         return htn_block_trdots_z(A, B, items_dev, n_items, out, n_out, trd_scratch, st);
     }
+    int block_place(void* dst, const void* src, const htn_place_item* items_dev, const htn_place_item* items_host, int n_items) override {
+        (void)items_host;
+        return htn_block_place_z(dst, src, items_dev, n_items, st);
+    }
     int batched_copy(void* dst, const void* src, const int32_t* idx, const double* scl, const htn_copy_item* items, int n_items,
                      double gscale) override {
         return htn_batched_copy_z(dst, src, idx, scl, items, n_items, gscale, st);

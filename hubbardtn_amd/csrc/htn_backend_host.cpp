@@ -333,6 +333,36 @@ int Backend::block_trdots(const void* A, const void* B, const htn_trdot_item* it
     return upload(out, res.data(), sizeof(cplx) * res.size());
 }
 
+int Backend::block_place(void* dst, const void* src, const htn_place_item* items_dev, const htn_place_item* items, int n_items) {
+    (void)items_dev;
+    if (n_items <= 0) return 0;
+    if (!items) return set_error("block_place: the host copy of the items is required");
+    int64_t d0 = INT64_MAX, d1 = 0, s0 = INT64_MAX, s1 = 0;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_place_item& it = items[q];
+        if (it.rows <= 0 || it.cols <= 0) continue;
+        d0 = std::min(d0, it.dst_off), d1 = std::max(d1, it.dst_off + (int64_t)(it.cols - 1) * it.ldd + it.rows);
+        if (it.src_off >= 0) s0 = std::min(s0, it.src_off), s1 = std::max(s1, it.src_off + (int64_t)(it.cols - 1) * it.lds + it.rows);
+    }
+    std::vector<cplx> hd((size_t)std::max<int64_t>(d1 - d0, 0)), hs((size_t)std::max<int64_t>(s1 - s0, 0));
+    if (hd.empty()) return 0;
+    // (the views need not cover the range between them: what lies there is read first and written back as it was)
+    if (download(hd.data(), (const cplx*)dst + d0, sizeof(cplx) * hd.size())) return 1;
+    if (!hs.empty() && download(hs.data(), (const cplx*)src + s0, sizeof(cplx) * hs.size())) return 1;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_place_item& it = items[q];
+        if (it.rows <= 0 || it.cols <= 0) continue;
+        cplx* d = hd.data() + (it.dst_off - d0);
+        const cplx* s = it.src_off >= 0 ? hs.data() + (it.src_off - s0) : nullptr;
+        for (int64_t c = 0; c < it.cols; ++c)
+            for (int64_t r = 0; r < it.rows; ++r) {
+                const cplx x = s ? s[r + c * it.lds] : cplx(0.0, 0.0);
+                d[r + c * it.ldd] = s ? cplx(it.coef * x.real(), it.coef * x.imag()) : cplx(0.0, 0.0);
+            }
+    }
+    return upload((cplx*)dst + d0, hd.data(), sizeof(cplx) * hd.size());
+}
+
 // ---- the kernel-level entries that have a host-memory statement: what the CPU baseline library exports ------------------
 extern "C" {
 

@@ -210,6 +210,16 @@ int htn_mps_correlator(htn_mps* mps, const htn_corr_channel* ch, void* out_host,
     if (mps->be->activate()) return 1;
     return mps->correlator(*ch, (cplx*)out_host, norm_host);
 }
+int htn_mps_apply_op(const htn_mps* src, int32_t site, const htn_site_op* op, htn_mps** out, double* norm2_host) {
+    if (!src || !op || !out) return set_error("htn_mps_apply_op: bad arguments");
+    if (src->be->activate()) return 1;
+    return const_cast<htn_mps*>(src)->apply_op(site, op, out, norm2_host);      // (the source's plan cache is the only thing written)
+}
+int htn_mps_transition(htn_mps* bra, const htn_site_op* op, const htn_mps* ket, void* out_host) {
+    if (!bra || !op || !ket || !out_host) return set_error("htn_mps_transition: bad arguments");
+    if (bra->be->activate()) return 1;
+    return bra->transition(op, ket, (cplx*)out_host);
+}
 
 // ---- queries of the state ------------------------------------------------------------------------------------------
 int64_t htn_mps_theta_size(htn_mps* mps, int32_t i) {

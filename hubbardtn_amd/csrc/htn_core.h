@@ -353,6 +353,10 @@ struct Backend {
     // upload -- what the CPU baseline library runs; the HIP backend overrides it with the kernel.
     virtual int block_trdots(const void* A, const void* B, const htn_trdot_item* items_dev, const htn_trdot_item* items_host,
                              int n_items, void* out, int n_out);
+    // dst view of every item = coef * src view, or zeros for src_off = -1 (htn_block_place_z in the header).  Default
+    // (htn_backend_host.cpp): download the ranges the items touch, place on the host, upload -- what the CPU baseline library
+    // runs; the HIP backend overrides it with the kernel.
+    virtual int block_place(void* dst, const void* src, const htn_place_item* items_dev, const htn_place_item* items_host, int n_items);
     virtual int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host,
                            int n_blocks, int max_m, int max_sweeps, double tol, int32_t* info_dev,
                            const htn_svd_opts* opts) = 0;

@@ -211,6 +211,13 @@ struct htn_mps {
     std::vector<OrthState> orth;        // htn_mps_set_orthogonal: the sweep stays in the orthogonal complement of these states
     int orth_dropped = 0;               // projector vectors dropped as numerically dependent in the last bond update
     int centre = 0;                     // site that carries the centre (htn_mps_create: 0; every update moves it)
+    // Every update normalises the tensors it writes.  A state made by htn_mps_apply_op carries <O psi|O psi> in its tensors
+    // (raw_n2 >= 0) until its first update, and from then on beside them: the state is amp x (the stored tensors).  Overlaps and
+    // transition amplitudes multiply by amp; every other state has amp = 1 and raw_n2 < 0 for life.
+    double amp = 1.0, raw_n2 = -1.0;
+    void norm_absorbed() {
+        if (raw_n2 >= 0.0) amp = sqrt(raw_n2), raw_n2 = -1.0;
+    }
 
     template <class T, class F>
     std::shared_ptr<T> cached(const std::string& key, F build) {
@@ -345,6 +352,9 @@ struct htn_mps {
     int set_orthogonal(const htn_mps* const* others, int n);      // htn_mps_set_orthogonal
     int overlap(const htn_mps* ket, double* out_host);            // htn_mps_overlap
     int correlator(const htn_corr_channel& ch, cplx* out_host, double* norm_host);
+    // ---- htn_applyop.cpp: a local operator applied to the state, transition amplitudes of all sites ----
+    int apply_op(int site, const htn_site_op* op, htn_mps** out, double* norm2_host);      // htn_mps_apply_op (this = the source, only read)
+    int transition(const htn_site_op* op, const htn_mps* ket, cplx* out_host);             // htn_mps_transition (this = the bra)
 };
 
 // ---- pieces of the engine that more than one file uses ------------------------------------------------------------------

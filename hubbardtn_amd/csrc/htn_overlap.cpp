@@ -136,6 +136,7 @@ int htn_mps::overlap(const htn_mps* b, double* out_host) {
     if (lay->size != 1) return set_error("htn_mps_overlap: the right end bonds are not one sector of dimension 1");
     cplx v;
     if (be->download(&v, buf.ptr(), sizeof(v))) return 1;
+    if (amp != 1.0 || b->amp != 1.0) v *= amp * b->amp;      // (states made by htn_mps_apply_op: htn_engine.h)
     out_host[0] = v.real();
     out_host[1] = v.imag();
     return 0;

@@ -1313,7 +1313,12 @@ void truncate(const std::vector<double>& vals, const std::vector<int>& lens, con
             std::push_heap(heap.begin(), heap.end(), worse);
         }
     }
-    trunc_weight = total > 0.0 ? (total - kept_w) / total : 0.0;
+    // the discarded weight is summed over what was discarded (the kept values are a prefix of every sector): total - kept_w
+    // cancels to an ulp of the total, 1e-16, where the true value is zero or the 1e-30 of values below the floor
+    double disc = 0.0;
+    for (size_t k = 0; k < nsec; ++k)
+        for (int i = counts[k]; i < lens[k]; ++i) disc += vals[start[k] + i] * vals[start[k] + i];
+    trunc_weight = total > 0.0 ? disc / total : 0.0;
     kept_norm = sqrt(kept_w);
 }
 

@@ -129,6 +129,7 @@ int htn_mps::update_site(int i, int direction, bool optimise, const htn_sweep_op
         site_buf[i] = out;
     }
     energy = s.E;
+    norm_absorbed();
     if (st) fill_stats(st, crossed, direction, s, Llay[i]->size + Rlay[i + 1]->size, 0, 0, 0.0, clk);
     return 0;
 }
@@ -169,6 +170,7 @@ int htn_mps::evolve_site(int i, cplx dt, const htn_sweep_opts& o, htn_bond_stats
     if (site_solve(i, *lay, *lay, true, &dt, o, clk, w)) return 1;
     const Solve& s = w.sol;
     site_buf[i] = w.out;
+    norm_absorbed();
     if (log_growth) *log_growth += log(s.growth);
     if (st) fill_stats(st, i, 0, s, Llay[i]->size + Rlay[i + 1]->size, 0, 0, 0.0, clk);
     return 0;

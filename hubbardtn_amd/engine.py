@@ -657,6 +657,50 @@ class DMRG2:
             Cm = Cm - np.outer(m, m)
         return Cm
 
+    # ---- local operators applied to the state (htn_mps_apply_op / htn_mps_transition) ------------------
+    OP_ALIASES = {"c+": "cdag", "c+_up": "cdag_up", "c+_dn": "cdag_dn"}
+
+    def _op_arg(self, op) -> abi.SiteOp:
+        """a site operator by name (a key of the symmetry's site_ops; "c+" stands for "cdag") or as an abi.SiteOp"""
+        if isinstance(op, abi.SiteOp):
+            return op
+        name = op if op in self.sym.site_ops else self.OP_ALIASES.get(op, op)
+        if name not in self.sym.site_ops:
+            raise ValueError(f"site operator '{op}' is not defined in the {self.sym.name} mode")
+        return self._site_op(name)
+
+    def move_centre(self, site):
+        """carry the centre to `site` by non-optimising, non-truncating two-site updates"""
+        if not 0 <= site < self.L:
+            raise ValueError(f"site {site} out of range (the chain has {self.L} sites)")
+        while self.centre() < site:
+            self.update_bond(self.centre(), +1, "right", optimise=False, record=False, cutoff=0.0)
+        while self.centre() > site:
+            self.update_bond(self.centre() - 1, -1, "left", optimise=False, record=False, cutoff=0.0)
+
+    def apply_op(self, site, op):
+        """a NEW engine holding O_site |self> (same context, MPO and solver settings; not normalised: `applied_norm2` of the result
+        is <O psi|O psi> = sum over the operator's components of <psi|O+_q O_q|psi>).  The centre must be on `site` and stays
+        there in the result; self is only read.  op: a site-operator name of the symmetry ("c", "cdag" = "c+", "n", "S", spinful
+        mode "c_up", "cdag_up", ...) or an abi.SiteOp.  SU(2) kinds: self has total spin 0 or the operator rank 0.
+        Every update normalises the tensors it writes: after its first update the result keeps its norm in a factor inside the
+        library, which `overlap` and `transition` apply; `copy()` goes through the tensors alone and gives the normalised state."""
+        o = self._op_arg(op)
+        h, n2 = C.c_void_p(), C.c_double(0.0)
+        self._check(self.lib.htn_mps_apply_op(self.handle, int(site), C.byref(o), C.byref(h), C.byref(n2)), "htn_mps_apply_op")
+        new = DMRG2.wrap(self.ops, self.cmpo, h, self.chi_full, self.cutoff, self.krylovdim, self.lanczos_tol, self.maxrestart,
+                         self.weighting, self.jacobi_tol, self.jacobi_max_sweeps)
+        new.applied_norm2 = n2.value
+        return new
+
+    def transition(self, op, ket) -> np.ndarray:
+        """ndarray[L]: <O_x self|ket> for every site x in one pass on the device (self in any gauge, not modified); ket lives in
+        the total sector of self fused with the operator's charge, e.g. an applied state after some time steps"""
+        o = self._op_arg(op)
+        out = np.zeros(self.L, dtype=np.complex128)
+        self._check(self.lib.htn_mps_transition(self.handle, C.byref(o), ket.handle, out.ctypes.data), "htn_mps_transition")
+        return out
+
     def site_energies(self):
         """genuine <psi|H|psi> of the state as stored, split per site: e_i = energy of all Hamiltonian terms that END
         on site i (on-site terms of i, and every two-site term whose right-most site is i); sum(e) = <psi|H|psi>.

@@ -318,6 +318,23 @@ int htn_block_trdots_z(const void* A, const void* B, const htn_trdot_item* items
                        void* out, int32_t n_out, void* scratch, void* stream);
 
 
+/* Block placement: builds a block-sparse tensor out of scaled blocks of another one (the site tensors of a state a local
+ * operator was applied to: htn_mps_apply_op, htn_mps_transition).  Per item
+ *   dst[dst_off + r + c*ldd] = coef * src[src_off + r + c*lds]   (0 <= r < rows, 0 <= c < cols),   or 0 when src_off = -1;
+ * column-major complex128, coef real (one rounding per component).  htn_batched_copy_z has one scale per launch and cannot
+ * zero-fill.  The items of a launch are expected to tile their destination exactly once, so no memset precedes it; nothing
+ * outside the items' views is written.  Items are cut into 32 x 32 tiles that are dealt over the workgroups of the launch
+ * (a large block is shared by all of them, many small ones share a workgroup); every element is written by exactly one
+ * thread, no atomics, repeated calls are bit-identical.  n_items = 0 is a no-op.  items: device array. */
+typedef struct {
+    int64_t dst_off, src_off;   /* element offsets into dst and src; src_off = -1: write zeros        */
+    int32_t rows, cols, ldd, lds;
+    double coef;
+    int32_t pad[6];             /* (pads the record to 64 bytes, the size of the other task records)  */
+} htn_place_item;               /* 64 bytes */
+int htn_block_place_z(void* dst, const void* src, const htn_place_item* items, int32_t n_items, void* stream);
+
+
 /* =====================================================================================================
  * Bond-update / sweep level (ABI 2): what sits behind
  *     find_groundstate(psi0, H, IDMRG2(; trscheme, tol))          src/HubbardFunctions.jl:1010
@@ -554,6 +571,29 @@ typedef struct {
     int32_t has_onsite, pad;
 } htn_corr_channel;                 /* 552 bytes */
 int htn_mps_correlator(htn_mps* mps, const htn_corr_channel* ch, void* out_host, double* norm_host);
+
+/* A reduced site operator O (rank k, charge dN) applied to site `site` of a finite open chain: *out is a NEW state
+ * O_site |src> in the total sector fused with (dN, k), on the same context and MPO; src is only read.  The operator's charge
+ * leaves through the right end: bonds right of the site are re-labelled by fusion with (dN, k) (an old sector contributes its
+ * multiplets to every new sector it couples to, in the sorted order of the old sectors; pairs nothing reaches are left out),
+ * the site's tensor is opened with the reduced elements, the tensors right of it are passed through with 6j recoupling
+ * coefficients; a fermionic operator carries its Jordan-Wigner string to the left, (-1)^(N_left dN).
+ * The centre of src must be on `site`; the result has its centre there too, is canonical, and is NOT normalised:
+ *   <O_x psi|O_y psi> = sum_q <psi| O+_{x,q} O_{y,q} |psi>   (sum over the components of the operator's multiplet)
+ * in the units of htn_mps_overlap; norm2_host (may be NULL) receives <out|out>.  A result of norm 0 is returned as it is.
+ * Host work: bond tables, layouts and one place-item list per site (cached by tables + operator); device work: one
+ * htn_block_place_z launch per site from `site` on, copies left of it, the H environments of the new tables.
+ * Errors: centre elsewhere; site out of range; SU(2) kinds: a source of total spin > 0 with an operator of rank > 0 (the result's
+ * sector would not be unique); a chain with boundary environments; a context with a communicator or an exchange hook; a
+ * state with attached orthogonal states; an operator that maps two site states onto one. */
+int htn_mps_apply_op(const htn_mps* src, int32_t site, const htn_site_op* op, htn_mps** out, double* norm2_host);
+/* out_host[x] = <O_x bra|ket> for all sites x (L complex128) in one pass: left of x the bra's own tensors (one left overlap
+ * pass), right of x the passed tensors, which do not depend on x (one right overlap pass), per site one step with the opened
+ * tensor and one htn_block_trdots_z launch: about 3L overlap steps instead of L^2.  bra may be in any gauge and is not
+ * modified; nothing synchronises inside the pass.  Sites the sector tables admit no contribution for give exact zeros.
+ * Errors: different contexts, lengths or symmetries; the total sector of ket is not that of bra fused with (dN, k); the
+ * limits of htn_mps_apply_op (for the bra). */
+int htn_mps_transition(htn_mps* bra, const htn_site_op* op, const htn_mps* ket, void* out_host);
 
 /* y = H_eff(bond i, i+1) x on host vectors in the library's theta layout (size htn_mps_theta_size); tests and
  * Hermiticity checks.  x and y are complex128 host arrays. */
