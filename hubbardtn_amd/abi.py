@@ -47,6 +47,15 @@ assert TRDOT_DT.itemsize == 64
 PLACE_DT = np.dtype([("dst_off", "<i8"), ("src_off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("ldd", "<i4"), ("lds", "<i4"),
                      ("coef", "<f8"), ("pad", "<i4", (6,))], align=False)                                          # htn_place_item
 assert PLACE_DT.itemsize == 64
+NULLPROJ_DT = np.dtype([("r_off", "<i8"), ("q_off", "<i8"), ("m", "<i4"), ("n", "<i4"), ("k", "<i4"), ("ldr", "<i4"), ("ldq", "<i4"),
+                        ("side", "<i4"), ("out", "<i4"), ("pad", "<i4", (5,))], align=False)                        # htn_nullproj_item
+assert NULLPROJ_DT.itemsize == 64
+
+
+def nullproj_units(m, n, side):
+    """HTN_NULLPROJ_UNITS"""
+    return 0 if m <= 0 or n <= 0 else ((m if side else n) + 15) // 16
+
 
 # ---- bond-update / sweep level (ABI 2) ----
 SYM_SU2_U1, SYM_U1_U1, SYM_SU2 = 0, 1, 2
@@ -139,7 +148,7 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_site_update", "htn_dmrg1_sweep", "htn_mps_centre", "htn_mps_site_theta_size", "htn_heff1_apply",
                   "htn_qr_blocks_z", "htn_mps_correlator",
                   "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo",
-                  "htn_mps_apply_op", "htn_mps_transition"]
+                  "htn_mps_apply_op", "htn_mps_transition", "htn_block_nullproj_z", "htn_mps_variance"]
 
 
 class GemmLaunch(C.Structure):
@@ -274,6 +283,8 @@ def declare_engine(lib):
     lib.htn_mps_set_mpo.argtypes = [vp, vp]
     lib.htn_mps_apply_op.argtypes = [vp, i32, C.POINTER(SiteOp), C.POINTER(vp), C.POINTER(f64)]
     lib.htn_mps_transition.argtypes = [vp, C.POINTER(SiteOp), vp, vp]
+    lib.htn_block_nullproj_z.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp]
+    lib.htn_mps_variance.argtypes = [vp, vp, vp, C.POINTER(f64), vp]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

@@ -697,6 +697,51 @@ def spectral_function(res, q, omegas, eta):
     return A
 
 
+# ---- energy variance and extrapolation ---------------------------------------------------------------------------------
+def energy_variance(psi, H=None):
+    """two-site energy variance of a FiniteMPS (Hubig, Haegeman, Schollwoeck, PRB 97, 045125) -> result with .total, .site [L],
+    .bond [L - 1] and .energy = <psi|H|psi>; total = sum(site) + sum(bond) is <H^2> - <H>^2 of the normalised state exactly for an
+    MPO of range 1 (nearest-neighbour terms) and a lower bound for longer range.  It is the convergence measure of a state that
+    was never truncated (one-site sweeps, applied and evolved states) and the abscissa of `extrapolate_energy`.  Measured on the
+    device by engine.DMRG2.variance; psi is the same state afterwards, in the same gauge position.  H other than the state's
+    current MPO replaces it first (engine.DMRG2.set_mpo: centre on site 0), as in time_evolve."""
+    if isinstance(psi, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
+        raise NotImplementedError("energy_variance needs a chain length: it is measured on a finite chain "
+                                  "(pass L= / use a FiniteMPS), not on an InfiniteMPS")
+    eng = psi.engine
+    if H is not None and H is not eng.mpo and H is not eng.cmpo:
+        eng.set_mpo(H)
+    return eng.variance()
+
+
+class Extrapolation:
+    """result of extrapolate_energy: the line E = E0 + slope * variance"""
+
+    def __init__(self, E0, slope, residual):
+        self.E0, self.slope, self.residual = E0, slope, residual
+
+    def __iter__(self):
+        return iter((self.E0, self.slope, self.residual))
+
+    def __repr__(self):
+        return f"Extrapolation(E0={self.E0:.12g}, slope={self.slope:.6g}, residual={self.residual:.3e})"
+
+
+def extrapolate_energy(energies, variances):
+    """least-squares line through (variance, energy) pairs of states of growing bond dimension: -> Extrapolation with .E0 (the
+    intercept, E at variance 0), .slope and .residual (the 2-norm of the misfit; 0 for two points).  Host only.  The energy
+    error of a variational state is linear in its variance to leading order, which makes the variance the abscissa of choice."""
+    E, v = np.asarray(energies, dtype=float).ravel(), np.asarray(variances, dtype=float).ravel()
+    if E.shape != v.shape or E.size < 2:
+        raise ValueError("extrapolate_energy: needs at least two (energy, variance) pairs of equal number")
+    if np.ptp(v) == 0.0:
+        raise ValueError("extrapolate_energy: all variances are equal, the line is not determined")
+    vm, Em = v.mean(), E.mean()
+    slope = float(np.sum((v - vm) * (E - Em)) / np.sum((v - vm) ** 2))
+    E0 = float(Em - slope * vm)
+    return Extrapolation(E0, slope, float(np.linalg.norm(E - (E0 + slope * v))))
+
+
 def TruncState(simul: Simulation, trunc_dim: int, trunc_scheme: int = 0, L: int | None = None, polish: str = "twosite", **kw):
     """truncated approximation of the ground state at bond dimension `trunc_dim` (TensorKit dim units), src:1351-1367.
     trunc_scheme 1 = SvdCut (truncate by SVD only); 0 = VUMPSSvdCut (truncate, then re-optimise variationally at

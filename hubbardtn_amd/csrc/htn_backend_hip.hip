@@ -76,6 +76,8 @@ struct HipBackend : htn::Backend {
     int64_t lan_scratch_elems = 0;
     void* trd_scratch = nullptr;                  // partial sums of block_trdots
     int64_t trd_scratch_elems = 0;
+    void* np_scratch = nullptr;                   // unit sums of block_nullproj (doubles)
+    int64_t np_scratch_elems = 0;
     void* comm = nullptr;
     char* stage = nullptr;                        // pinned host staging ring of upload()
     size_t stage_cap = (size_t)32 << 20, stage_pos = 0;
@@ -93,6 +95,7 @@ struct HipBackend : htn::Backend {
         for (auto& kv : live) (void)hipFree(kv.first);
         if (lan_scratch) (void)hipFree(lan_scratch);
         if (trd_scratch) (void)hipFree(trd_scratch);
+        if (np_scratch) (void)hipFree(np_scratch);
         if (stage) (void)hipHostFree(stage);
         if (land) (void)hipHostFree(land);
         if (own_stream && st) (void)hipStreamDestroy(st);
@@ -324,6 +327,20 @@ struct HipBackend : htn::Backend {
     int block_place(void* dst, const void* src, const htn_place_item* items_dev, const htn_place_item* items_host, int n_items) override {
         (void)items_host;
         return htn_block_place_z(dst, src, items_dev, n_items, st);
+    }
+    int block_nullproj(void* R, const void* Q, const htn_nullproj_item* items_dev, const htn_nullproj_item* items_host, int n_items, double* out,
+                       int n_out) override {
+        if (n_items > 0 && !items_host) return htn::set_error("block_nullproj: the host copy of the items is required");
+        int64_t need = 1;
+        for (int q = 0; q < n_items; ++q) need += 2 * (int64_t)HTN_NULLPROJ_UNITS(items_host[q].m, items_host[q].n, items_host[q].side);
+        if (need > np_scratch_elems) {               // (hipFree waits for the launches that still read the old block)
+            if (np_scratch) HIP_TRY(hipFree(np_scratch));
+            np_scratch = nullptr, np_scratch_elems = 0;
+            HIP_TRY(hipMalloc(&np_scratch, sizeof(double) * 2 * need));
+            np_scratch_elems = 2 * need;
+            if (htn_debug_poison()) HIP_TRY(hipMemsetAsync(np_scratch, 0xFF, sizeof(double) * np_scratch_elems, st));
+        }
+        return htn_block_nullproj_z(R, Q, items_dev, items_host, n_items, out, n_out, np_scratch, st);
     }
     int batched_copy(void* dst, const void* src, const int32_t* idx, const double* scl, const htn_copy_item* items, int n_items,
                      double gscale) override {

@@ -1,5 +1,5 @@
 // Host statements of the htn::Backend methods that are not pure (htn_core.h), and of the two kernel-level entries that have
-// one (htn_krylov_expm_z, htn_qr_blocks_z): vectors downloaded, H applied through the backend's grouped_gemm, the arithmetic
+// one (htn_krylov_expm_z, htn_qr_blocks_z, htn_block_nullproj_z): vectors downloaded, H applied through the backend's grouped_gemm, the arithmetic
 // in plain C++.  The CPU baseline library runs them; the HIP backend overrides every one with its kernels.  Nothing here
 // uses the sweep engine's types.  Host C++ (no HIP).
 // NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
@@ -363,6 +363,87 @@ int Backend::block_place(void* dst, const void* src, const htn_place_item* items
     return upload((cplx*)dst + d0, hd.data(), sizeof(cplx) * hd.size());
 }
 
+// Null-space projection on host memory (conventions of htn_block_nullproj_z): per item W = Q^H R, R -= Q W (side 0) or W = R Q^H,
+// R -= W Q (side 1), twice; out[2 o] += |W|^2 of the first pass, out[2 o + 1] += |R|^2 at the end, items in list order
+int htn::nullproj_host(cplx* Rb, const cplx* Qb, const htn_nullproj_item* items, int n_items, double* out, int n_out) {
+    for (int o = 0; o < 2 * n_out; ++o) out[o] = 0.0;
+    std::vector<cplx> W;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_nullproj_item& it = items[q];
+        if (it.out < 0 || it.out >= n_out) return set_error("block_nullproj: item %d adds to result %d of %d", q, it.out, n_out);
+        if (it.m <= 0 || it.n <= 0) continue;
+        const int64_t m = it.m, n = it.n, k = it.k, ldr = it.ldr, ldq = it.ldq;
+        cplx* R = Rb + it.r_off;
+        const cplx* Q = Qb + it.q_off;
+        double w2 = 0.0, r2 = 0.0;
+        for (int pass = 0; pass < 2 && k > 0; ++pass) {
+            if (it.side == 0) {
+                W.assign((size_t)(k * n), cplx(0.0, 0.0));
+                for (int64_t c = 0; c < n; ++c)
+                    for (int64_t t = 0; t < k; ++t) {
+                        cplx s = 0.0;
+                        for (int64_t i = 0; i < m; ++i) s += std::conj(Q[i + t * ldq]) * R[i + c * ldr];
+                        W[(size_t)(t + c * k)] = s;
+                    }
+                for (int64_t c = 0; c < n; ++c)
+                    for (int64_t t = 0; t < k; ++t) {
+                        const cplx w = W[(size_t)(t + c * k)];
+                        for (int64_t i = 0; i < m; ++i) R[i + c * ldr] -= Q[i + t * ldq] * w;
+                    }
+            } else {
+                W.assign((size_t)(m * k), cplx(0.0, 0.0));
+                for (int64_t t = 0; t < k; ++t)
+                    for (int64_t c = 0; c < n; ++c) {
+                        const cplx qc = std::conj(Q[t + c * ldq]);
+                        for (int64_t i = 0; i < m; ++i) W[(size_t)(i + t * m)] += R[i + c * ldr] * qc;
+                    }
+                for (int64_t c = 0; c < n; ++c)
+                    for (int64_t t = 0; t < k; ++t) {
+                        const cplx qv = Q[t + c * ldq];
+                        for (int64_t i = 0; i < m; ++i) R[i + c * ldr] -= W[(size_t)(i + t * m)] * qv;
+                    }
+            }
+            if (pass == 0)
+                for (const cplx& w : W) w2 += std::norm(w);
+        }
+        for (int64_t c = 0; c < n; ++c)
+            for (int64_t i = 0; i < m; ++i) r2 += std::norm(R[i + c * ldr]);
+        out[2 * it.out] += w2;
+        out[2 * it.out + 1] += r2;
+    }
+    return 0;
+}
+
+int Backend::block_nullproj(void* R, const void* Q, const htn_nullproj_item* items_dev, const htn_nullproj_item* items, int n_items,
+                            double* out, int n_out) {
+    (void)items_dev;
+    if (n_out <= 0) return 0;
+    if (n_items > 0 && !items) return set_error("block_nullproj: the host copy of the items is required");
+    int64_t r0 = INT64_MAX, r1 = 0, q0 = INT64_MAX, q1 = 0;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_nullproj_item& it = items[q];
+        if (it.m <= 0 || it.n <= 0) continue;
+        r0 = std::min(r0, it.r_off), r1 = std::max(r1, it.r_off + (int64_t)(it.n - 1) * it.ldr + it.m);
+        if (it.k > 0) {
+            const int64_t qr = it.side ? it.k : it.m, qc = it.side ? it.n : it.k;
+            q0 = std::min(q0, it.q_off), q1 = std::max(q1, it.q_off + (qc - 1) * it.ldq + qr);
+        }
+    }
+    std::vector<cplx> hr((size_t)std::max<int64_t>(r1 - r0, 0)), hq((size_t)std::max<int64_t>(q1 - q0, 0));
+    std::vector<double> res((size_t)(2 * n_out), 0.0);
+    // (the views need not cover the range between them: what lies there is read first and written back as it was)
+    if (!hr.empty() && download(hr.data(), (const cplx*)R + r0, sizeof(cplx) * hr.size())) return 1;
+    if (!hq.empty() && download(hq.data(), (const cplx*)Q + q0, sizeof(cplx) * hq.size())) return 1;
+    std::vector<htn_nullproj_item> d(items, items + n_items);
+    for (auto& it : d) {
+        it.r_off -= hr.empty() ? it.r_off : r0;
+        it.q_off -= hq.empty() || it.k <= 0 ? it.q_off : q0;
+    }
+    if (nullproj_host(hr.data(), hq.data(), d.data(), n_items, res.data(), n_out)) return 1;
+    if (!hr.empty() && upload((cplx*)R + r0, hr.data(), sizeof(cplx) * hr.size())) return 1;
+    return upload(out, res.data(), sizeof(double) * res.size());
+}
+
 // ---- the kernel-level entries that have a host-memory statement: what the CPU baseline library exports ------------------
 extern "C" {
 
@@ -397,6 +478,23 @@ __attribute__((weak)) int htn_qr_blocks_z(void* A, void* Rbuf, const htn_qr_bloc
             return set_error("htn_qr_blocks_z: block %d: m = %d, n = %d, ld = %d, ldr = %d (need m >= n >= 1)", b, d[b].m, d[b].n, d[b].ld, d[b].ldr);
     qr_blocks_host((cplx*)A, (cplx*)Rbuf, d, n_blocks);
     return 0;
+}
+
+// Host-memory statement of the kernel-level entry (plain loops): what the CPU baseline library exports.  Weak: in
+// libhubbardtn_hip.so the definition of htn_nullproj.hip (device pointers, the gfx950 kernel) takes its place at link time.
+__attribute__((weak)) int htn_block_nullproj_z(void* R, const void* Q, const htn_nullproj_item* items, const htn_nullproj_item* items_host,
+                                               int32_t n_items, double* out, int32_t n_out, void* scratch, void* stream) {
+    (void)scratch, (void)stream;
+    if (n_items < 0 || n_out < 0) return set_error("htn_block_nullproj_z: negative count");
+    if (n_out == 0) return 0;
+    const htn_nullproj_item* d = items_host ? items_host : items;
+    if (!out || (n_items > 0 && (!d || !R))) return set_error("htn_block_nullproj_z: bad arguments");
+    for (int q = 0; q < n_items; ++q)
+        if (d[q].m < 0 || d[q].n < 0 || d[q].k < 0 || (d[q].side != 0 && d[q].side != 1) ||
+            (d[q].m > 0 && d[q].n > 0 && (d[q].ldr < d[q].m || (d[q].k > 0 && (!Q || d[q].ldq < (d[q].side ? d[q].k : d[q].m))))))
+            return set_error("htn_block_nullproj_z: item %d: m = %d, n = %d, k = %d, ldr = %d, ldq = %d, side = %d", q, d[q].m, d[q].n, d[q].k,
+                             d[q].ldr, d[q].ldq, d[q].side);
+    return nullproj_host((cplx*)R, (const cplx*)Q, d, n_items, out, n_out);
 }
 
 }  // extern "C"

@@ -357,6 +357,12 @@ struct Backend {
     // (htn_backend_host.cpp): download the ranges the items touch, place on the host, upload -- what the CPU baseline library
     // runs; the HIP backend overrides it with the kernel.
     virtual int block_place(void* dst, const void* src, const htn_place_item* items_dev, const htn_place_item* items_host, int n_items);
+    // R view of every item <- what is left of it outside the range of the item's isometry Q, projected twice; out[2 o], out[2 o + 1]
+    // (device doubles) = |removed coefficients|^2 of the first pass, |R|^2 at the end, summed over the items of result o
+    // (htn_block_nullproj_z in the header).  Default (htn_backend_host.cpp): download the ranges the items touch, plain loops on
+    // the host, upload -- what the CPU baseline library runs; the HIP backend overrides it with the kernel.
+    virtual int block_nullproj(void* R, const void* Q, const htn_nullproj_item* items_dev, const htn_nullproj_item* items_host, int n_items,
+                               double* out, int n_out);
     virtual int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host,
                            int n_blocks, int max_m, int max_sweeps, double tol, int32_t* info_dev,
                            const htn_svd_opts* opts) = 0;
@@ -374,6 +380,8 @@ Backend* make_backend(int backend, int device, void* stream);       // one per l
 
 // Householder QR / LQ of the blocks on HOST memory, conventions of htn_qr_blocks_z
 void qr_blocks_host(cplx* A, cplx* R, const htn_qr_block* desc, int n_blocks);
+// null-space projection of the items on HOST memory, conventions of htn_block_nullproj_z (every one of the n_out results is written)
+int nullproj_host(cplx* R, const cplx* Q, const htn_nullproj_item* items, int n_items, double* out, int n_out);
 
 int set_error(const char* fmt, ...);        // writes the thread-local error string, returns 1
 char* err_buf();

@@ -320,6 +320,19 @@ class HipOps:
         abi.check(self.lib, self.lib.htn_qr_blocks_z(self._p(A), self._p(R), self._p(desc_dev), desc_host.ctypes.data, nblocks,
                                                      self._stream()), "htn_qr_blocks_z")
 
+    def block_nullproj(self, R, Q, items, n_out):
+        """htn_block_nullproj_z: the R views of `items` (host array of abi.NULLPROJ_DT) <- what is left of them outside the range of
+        their isometries in Q, projected twice, in place; -> device float64 tensor [n_out, 2]: |removed coefficients|^2 of the
+        first pass, |R|^2 at the end, summed over the items of each result"""
+        items = np.ascontiguousarray(items, dtype=abi.NULLPROJ_DT)
+        units = sum(abi.nullproj_units(int(it["m"]), int(it["n"]), int(it["side"])) for it in items)
+        scratch = self.empty_f64(2 * units + 2)
+        out = self.empty_f64(2 * max(n_out, 1))
+        dev = self.to_device(items) if len(items) else None
+        abi.check(self.lib, self.lib.htn_block_nullproj_z(self._p(R), self._p(Q), self._p(dev), items.ctypes.data, len(items),
+                                                          self._p(out), n_out, self._p(scratch), self._stream()), "htn_block_nullproj_z")
+        return out.view(max(n_out, 1), 2)[:n_out]
+
     def batched_copy(self, dst, src, idx, scl, items_dev, nitems, gscale):
         if nitems == 0:
             return

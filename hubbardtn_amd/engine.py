@@ -153,6 +153,16 @@ def state_tables(bonds, tensors) -> StateTables:
                        np.array(data_ptr, dtype=np.int64), data)
 
 
+class Variance:
+    """result of DMRG2.variance / api.energy_variance"""
+
+    def __init__(self, total, site, bond, energy, split=None):
+        self.total, self.site, self.bond, self.energy, self.split = total, site, bond, energy, split
+
+    def __repr__(self):
+        return f"Variance(total={self.total:.6e}, energy={self.energy:.12g})"
+
+
 class DMRG2:
     """finite two-site DMRG on reduced SU(2) x U(1) tensors -- handle of an `htn_mps` inside the library.
 
@@ -700,6 +710,22 @@ class DMRG2:
         out = np.zeros(self.L, dtype=np.complex128)
         self._check(self.lib.htn_mps_transition(self.handle, C.byref(o), ket.handle, out.ctypes.data), "htn_mps_transition")
         return out
+
+    # ---- two-site energy variance (htn_mps_variance) ----------------------------------------------------
+    def variance(self, timed=False):
+        """two-site energy variance of the state as stored (Hubig, Haegeman, Schollwoeck, PRB 97, 045125): -> Variance with
+        .total = sum(.site) + sum(.bond), .site[L] (one-site residuals), .bond[L - 1] (two-site residuals), .energy = <psi|H|psi>.
+        Exact (<H^2> - <H>^2) for an MPO of range 1, a lower bound for longer range.  One library call; the centre may be
+        anywhere and is back where it was afterwards, the state is the same state (to rounding), `energy` and `stats` are left
+        alone.  An applied state reports the variance of the normalised state.  timed=True also fills .split = seconds spent in
+        (theta + applies, projections, moves), each closed by a stream sync."""
+        self.__dict__.pop("_bond_cache", None)
+        site, bond = np.zeros(self.L), np.zeros(max(self.L - 1, 1))
+        E, split = C.c_double(0.0), np.zeros(3)
+        self._check(self.lib.htn_mps_variance(self.handle, site.ctypes.data, bond.ctypes.data, C.byref(E),
+                                              split.ctypes.data if timed else None), "htn_mps_variance")
+        bond = bond[:self.L - 1]
+        return Variance(float(site.sum() + bond.sum()), site, bond, E.value, tuple(split) if timed else None)
 
     def site_energies(self):
         """genuine <psi|H|psi> of the state as stored, split per site: e_i = energy of all Hamiltonian terms that END

@@ -335,6 +335,40 @@ typedef struct {
 int htn_block_place_z(void* dst, const void* src, const htn_place_item* items, int32_t n_items, void* stream);
 
 
+/* Batched null-space projection: what is left of a block outside the range of an isometry, and how much was removed.  The
+ * projected residuals of the two-site energy variance (htn_mps_variance): y (1 - A A^H) from the left, (1 - B^H B) from the right.
+ * Per item R is an m x n view (column-major complex128, leading dimension ldr) inside `R`, Q a view inside `Q`:
+ *   side 0 : Q is m x k with orthonormal columns (ldq >= m):  W = Q^H R,  R <- R - Q W
+ *   side 1 : Q is k x n with orthonormal rows    (ldq >= k):  W = R Q^H,  R <- R - W Q
+ * Every projection is applied TWICE (an isometry that is orthonormal to 1e-12 leaves that much of the removed part behind in
+ * one pass; a residual of 1e-7 of the block would drown in it).  Per result o two real numbers, sums over the items with
+ * item.out == o in list order:
+ *   out[2 o]     = |W|_F^2 of the FIRST pass (the removed coefficients)
+ *   out[2 o + 1] = |R|_F^2 after the second pass
+ * results with no item are written as 0.  k = 0 is a pure norm (R is not written); m = 0 or n = 0 contributes nothing.
+ * Work unit (HIP): (item, 16-column chunk of R) for side 0, (item, 16-row chunk) for side 1 -- HTN_NULLPROJ_UNITS per item --,
+ * one workgroup each; units touch disjoint parts of R, so a large block spreads over the device and no workgroup waits for
+ * another.  Inside a unit Q is taken in rounds of 64 columns (rows): the four waves form their shares of W over a quarter of
+ * the long dimension each on v_mfma_f64_16x16x4_f64, the shares are added in wave order in LDS, then every wave updates 16-row
+ * tiles of the chunk with the same instruction; any k >= 0.  No floating-point atomics: every unit stores its two partial
+ * sums, a second launch adds the units of an item in unit order and the items of a result in list order.  Repeated calls are
+ * bit-identical; nothing outside the R views is written.
+ * items: device array; items_host: the same array in host memory (needed: it sizes the launch); scratch: 2 x (sum of
+ * HTN_NULLPROJ_UNITS over the items) doubles.  The CPU baseline library exports the same entry on host memory (plain loops,
+ * the same two passes and outputs; items and scratch may be NULL there). */
+#define HTN_NULLPROJ_UNITS(m, n, side) ((m) <= 0 || (n) <= 0 ? 0 : (((side) ? (m) : (n)) + 15) / 16)
+typedef struct {
+    int64_t r_off, q_off;       /* element offsets of the views inside R and Q                        */
+    int32_t m, n, k;            /* R: m x n; Q: m x k (side 0) or k x n (side 1)                      */
+    int32_t ldr, ldq;
+    int32_t side;
+    int32_t out;                /* index of the result this item adds to                              */
+    int32_t pad[5];             /* (pads the record to 64 bytes, the size of the other task records)  */
+} htn_nullproj_item;            /* 64 bytes */
+int htn_block_nullproj_z(void* R, const void* Q, const htn_nullproj_item* items, const htn_nullproj_item* items_host,
+                         int32_t n_items, double* out, int32_t n_out, void* scratch, void* stream);
+
+
 /* =====================================================================================================
  * Bond-update / sweep level (ABI 2): what sits behind
  *     find_groundstate(psi0, H, IDMRG2(; trscheme, tol))          src/HubbardFunctions.jl:1010
@@ -594,6 +628,29 @@ int htn_mps_apply_op(const htn_mps* src, int32_t site, const htn_site_op* op, ht
  * Errors: different contexts, lengths or symmetries; the total sector of ket is not that of bra fused with (dN, k); the
  * limits of htn_mps_apply_op (for the bra). */
 int htn_mps_transition(htn_mps* bra, const htn_site_op* op, const htn_mps* ket, void* out_host);
+
+/* Two-site energy variance of a finite open chain (Hubig, Haegeman, Schollwoeck, Phys. Rev. B 97, 045125): the squared norms of
+ * (H - E)|psi> projected onto the one-site and the two-site tangent complements.  A sum of squared norms: no cancellation, no
+ * <H^2> environments, no SVD of its own.  EXACT (= <H^2> - <H>^2 of the normalised state) for an MPO of range 1 (nearest-
+ * neighbour terms only), a LOWER BOUND for longer range.  With the centre carried from site 0 to L-1, M_i the centre on site i,
+ * A_i the left isometry of M_i, B_{i+1} the stored right-canonical tensor, theta = M_i B_{i+1} and y = H_eff2 theta:
+ *   bond_host[i] = |(1 - A_i A_i^H) y (1 - B_{i+1}^H B_{i+1})|^2        i = 0 .. L-2
+ *   site_host[i] = |(1 - A_i A_i^H) y B_{i+1}^H|^2                      i = 0 .. L-2   (the left-null part of H_eff1(M_i))
+ *   site_host[L-1] = |H_eff1(M) - <M|H_eff1(M)> M|^2                    M the centre on the last site, formed by subtraction
+ *   *energy_host = <theta|y>;   the variance is sum(site) + sum(bond).
+ * In the tilde normalisation all of these are plain per-sector products and Frobenius norms.  Device work:
+ * per bond one theta, one H_eff2 apply, one non-optimising move (htn_bond_update with optimise = 0, no dimension limit, no
+ * cutoff: only singular values below 1e-14 of the largest go) that yields A_i, two htn_block_nullproj_z launches; one H_eff1 apply
+ * and one launch on the last site; ONE download of the results.  The centre may be anywhere: it is carried to site 0 first by
+ * the same moves.  No update writes into a buffer the state holds, so the state is kept by its handles and put back when the
+ * call returns (errors included): tensors, environments, centre, stored energy, spectra and hints are bit for bit what they
+ * were, and nothing is carried back.  Only the plan cache grows; the item lists are cached under keys of their own.
+ * A state that carries its norm beside its tensors (htn_mps_apply_op) reports the variance of the NORMALISED state.
+ * site_host: L doubles, bond_host: L-1 doubles, energy_host: one; each may be NULL.  split_host (may be NULL): three doubles, host
+ * wall seconds of [theta + applies, projections, moves], every lap closed by a stream sync (a timed call is slower).
+ * Refused: a chain with boundary environments (an iDMRG window), a context with a communicator or an exchange hook, a state
+ * with attached orthogonal states, a state of norm 0. */
+int htn_mps_variance(htn_mps* mps, double* site_host, double* bond_host, double* energy_host, double* split_host);
 
 /* y = H_eff(bond i, i+1) x on host vectors in the library's theta layout (size htn_mps_theta_size); tests and
  * Hermiticity checks.  x and y are complex128 host arrays. */

@@ -142,6 +142,14 @@ function export_mps(ψ::FiniteMPS, P::Int, Q::Int; offset::Int = 0)     # offset
     return bond_ptr, secs, sub_ptr, subs, data_ptr, data
 end
 
+# ---- two-site energy variance of the state behind `mps` (htn_mps_variance; not exercised by the tests) ------------------
+# -> (total, site[L], bond[L-1], energy); exact for an MPO of range 1, a lower bound for longer range
+function energy_variance(mps::Ptr{Cvoid}, L::Int)
+    site, bond, E = zeros(Float64, L), zeros(Float64, max(L - 1, 1)), Ref{Float64}(0.0)
+    check(ccall((:htn_mps_variance, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}), mps, site, bond, E, C_NULL))
+    return sum(site) + sum(bond[1:L-1]), site, bond[1:L-1], E[]
+end
+
 # ---- MPS import: htn_mps_bond / htn_mps_site_size / htn_mps_get_site per site -----------------------------------------
 # Builds new virtual spaces from the bond tables the library returns, allocates TensorMaps on them and copies every
 # sub-block into its fusion-tree window (undoing the tilde factor).  The centre is on site 1 after htn_dmrg2_sweep.
