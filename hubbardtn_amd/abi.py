@@ -148,7 +148,8 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_site_update", "htn_dmrg1_sweep", "htn_mps_centre", "htn_mps_site_theta_size", "htn_heff1_apply",
                   "htn_qr_blocks_z", "htn_mps_correlator",
                   "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo",
-                  "htn_mps_apply_op", "htn_mps_transition", "htn_block_nullproj_z", "htn_mps_variance"]
+                  "htn_mps_apply_op", "htn_mps_transition", "htn_block_nullproj_z", "htn_mps_variance",
+                  "htn_site_evolve_move", "htn_tdvp1_sweep", "htn_mps_bond_size", "htn_heff0_apply"]
 
 
 class GemmLaunch(C.Structure):
@@ -285,6 +286,11 @@ def declare_engine(lib):
     lib.htn_mps_transition.argtypes = [vp, C.POINTER(SiteOp), vp, vp]
     lib.htn_block_nullproj_z.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp]
     lib.htn_mps_variance.argtypes = [vp, vp, vp, C.POINTER(f64), vp]
+    lib.htn_site_evolve_move.argtypes = [vp, i32, i32, f64, f64, f64, f64, C.POINTER(SweepOpts), vp]
+    lib.htn_tdvp1_sweep.argtypes = [vp, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
+    lib.htn_mps_bond_size.argtypes = [vp, i32]
+    lib.htn_mps_bond_size.restype = i64
+    lib.htn_heff0_apply.argtypes = [vp, i32, vp, vp]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

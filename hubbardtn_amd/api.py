@@ -89,6 +89,17 @@ class TDVP2:
 
 
 @dataclass
+class TDVP:
+    """one-site TDVP selector (MPSKit.TDVP keyword names): time evolution at the state's current bond tables, nothing is
+    truncated (hence no trscheme).  Grow the bonds first -- two-site DMRG sweeps, or TDVP2 steps until the cap is reached -- then
+    switch to this on the same handle.  tol is the tolerance of the Krylov exponential, maxrestart the number of sub-steps a
+    solve may take when krylovdim vectors do not reach it."""
+    krylovdim: int = 30
+    tol: float = 1e-10
+    maxrestart: int = 8
+
+
+@dataclass
 class InfiniteHamiltonian:
     """the model of a translation-invariant chain; len() = sites per unit cell (length(H) in the reference)"""
     simul: Simulation
@@ -276,10 +287,12 @@ def find_groundstate(psi: FiniteMPS, H, alg: DMRG2, envs=None):
 def _tdvp_setup(psi, H, alg):
     if isinstance(psi, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
         raise NotImplementedError("time evolution of the infinite chain is not available: give a chain length L")
-    if not isinstance(alg, TDVP2):
+    if not isinstance(alg, (TDVP2, TDVP)):
         raise TypeError("timestep / time_evolve take alg = TDVP2(...)")
     eng = psi.engine
-    if isinstance(alg.trscheme, truncdim):
+    if isinstance(alg, TDVP):           # one-site: the bond tables stay, the truncation settings of the state are not touched
+        pass
+    elif isinstance(alg.trscheme, truncdim):
         eng.chi_full, eng.cutoff = int(alg.trscheme.D), 0.0
     elif isinstance(alg.trscheme, truncbelow):
         eng.chi_full, eng.cutoff = None, float(alg.trscheme.eta)
@@ -293,21 +306,28 @@ def _tdvp_setup(psi, H, alg):
     return eng
 
 
-def timestep(psi: FiniteMPS, H, dt, alg: TDVP2, envs=None):
-    """one two-site TDVP step psi <- exp(-i dt H) psi in place (MPSKit.timestep; dt complex, -i beta is imaginary time and the
-    state stays normalised).  H other than the state's current MPO replaces it first (engine.DMRG2.set_mpo).
-    -> (psi, envs)"""
+def _tdvp_step(eng, alg):
+    """the sweep of the selector: TDVP2 -> tdvp_sweep (two-site), TDVP -> tdvp1_sweep (one-site, fixed bond tables)"""
+    return eng.tdvp1_sweep if isinstance(alg, TDVP) else eng.tdvp_sweep
+
+
+def timestep(psi: FiniteMPS, H, dt, alg, envs=None):
+    """one TDVP step psi <- exp(-i dt H) psi in place (MPSKit.timestep; dt complex, -i beta is imaginary time and the state stays
+    normalised): two-site with alg = TDVP2(...), one-site at the current bond tables with alg = TDVP(...).  H other than the
+    state's current MPO replaces it first (engine.DMRG2.set_mpo).  -> (psi, envs)"""
     eng = _tdvp_setup(psi, H, alg)
-    eng.tdvp_sweep(dt)
+    _tdvp_step(eng, alg)(dt)
     return psi, Environments(eng)
 
 
-def time_evolve(psi: FiniteMPS, H, times, alg: TDVP2, observe=None):
+def time_evolve(psi: FiniteMPS, H, times, alg, observe=None):
     """evolve psi through the increasing list `times` (MPSKit.time_evolve; the state is at times[0] on entry), one TDVP step per
-    interval.  With observe: the list of observe(psi, t) for every t of `times`.  Without: a dict of arrays over the times --
-    "times", "energy" (<psi|H|psi>), "density_state" and "double_occupancy" ([len(times), L]), "loschmidt" (<psi(t0)|psi(t)>,
+    interval (alg = TDVP2(...) or TDVP(...), as for timestep; with TDVP "trunc_weight" is all zeros).  A hybrid run calls this
+    twice on one handle: times[:k] with TDVP2(truncdim(D)), then times[k-1:] with TDVP().
+    With observe: the list of observe(psi, t) for every t of `times`.  Without: a dict of arrays over the times -- "times", "energy" (<psi|H|psi>), "density_state" and "double_occupancy" ([len(times), L]), "loschmidt" (<psi(t0)|psi(t)>,
     complex) and "trunc_weight" (discarded weight of the step that led to each time, 0 for the first)."""
     eng = _tdvp_setup(psi, H, alg)
+    step = _tdvp_step(eng, alg)
     times = [complex(t) if isinstance(t, complex) else float(t) for t in times]
     out = []
     psi0 = None
@@ -323,7 +343,7 @@ def time_evolve(psi: FiniteMPS, H, times, alg: TDVP2, observe=None):
     out.append(record(times[0], 0.0))
     for t0, t1 in zip(times[:-1], times[1:]):
         k0 = len(eng.stats)
-        eng.tdvp_sweep(t1 - t0)
+        step(t1 - t0)
         out.append(record(t1, float(sum(s.trunc_weight for s in eng.stats[k0:]))))
     if observe is not None:
         return out
@@ -636,9 +656,10 @@ def apply_operator(psi, name, site):
     return FiniteMPS(work.apply_op(int(site), name), psi.L)
 
 
-def greens_function(psi0, H, times, alg: TDVP2, op="c+", site=None):
+def greens_function(psi0, H, times, alg, op="c+", site=None):
     """C[t, x] = exp(+i E0 t) <O_x psi0| exp(-i H t) O_site psi0> for all sites x and the increasing list `times` (the first entry
-    is the time of the applied state itself, normally 0), E0 = <psi0|H|psi0>, site = L // 2 by default.  One tdvp_sweep and one
+    is the time of the applied state itself, normally 0), E0 = <psi0|H|psi0>, site = L // 2 by default.  One TDVP sweep (alg =
+    TDVP2(...), or TDVP(...): one-site at the bond tables of the applied state, trunc_weight all zeros) and one
     `transition` pass per interval.  -> {"times", "C": [len(times), L], "E0", "trunc_weight", "site"}.
     The overlaps carry the sum over the components of the operator's multiplet (apply_operator), e.g. both spins for "c+" in
     the SU(2) modes.  The factor -i, the step function and the combination of the particle part (op = "c+") with the hole part
@@ -653,6 +674,7 @@ def greens_function(psi0, H, times, alg: TDVP2, op="c+", site=None):
     phi = apply_operator(psi0, op, site)
     phi.engine.move_centre(0)
     eng = _tdvp_setup(phi, H, alg)
+    step = _tdvp_step(eng, alg)
     ref = psi0.engine.copy()            # (bond_energies moves the centre through the chain: not on the caller's state)
     if H is not None and H is not ref.mpo and H is not ref.cmpo:
         ref.set_mpo(H)
@@ -662,7 +684,7 @@ def greens_function(psi0, H, times, alg: TDVP2, op="c+", site=None):
     Cm[0] = psi0.engine.transition(op, eng)
     for k in range(1, len(times)):
         k0 = len(eng.stats)
-        eng.tdvp_sweep(times[k] - times[k - 1])
+        step(times[k] - times[k - 1])
         tw[k] = float(sum(s.trunc_weight for s in eng.stats[k0:]))
         Cm[k] = np.exp(1j * E0 * (times[k] - times[0])) * psi0.engine.transition(op, eng)
     return {"times": np.array(times), "C": Cm, "E0": E0, "trunc_weight": tw, "site": site}

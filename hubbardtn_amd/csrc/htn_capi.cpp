@@ -185,6 +185,32 @@ int htn_tdvp2_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_op
     if (mps->be->activate()) return 1;
     return mps->tdvp2_sweep(cplx(dt_re, dt_im), norm_opts(opts), stats, energy, log_norm);
 }
+int htn_site_evolve_move(htn_mps* mps, int32_t i, int32_t direction, double fwd_re, double fwd_im, double back_re, double back_im,
+                         const htn_sweep_opts* opts, htn_bond_stats* stats) {
+    if (!mps) return set_error("htn_site_evolve_move: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->evolve_site_move(i, direction, cplx(fwd_re, fwd_im), cplx(back_re, back_im), norm_opts(opts), stats, nullptr);
+}
+int htn_tdvp1_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_opts* opts, htn_bond_stats* stats, double* energy,
+                    double* log_norm) {
+    if (!mps) return set_error("htn_tdvp1_sweep: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->tdvp1_sweep(cplx(dt_re, dt_im), norm_opts(opts), stats, energy, log_norm);
+}
+int64_t htn_mps_bond_size(htn_mps* mps, int32_t b) {
+    if (!mps || b < 0 || b > mps->L) return -1;
+    int64_t n = 0;
+    for (int d : mps->bonds[b]->dims) n += (int64_t)d * d;
+    return n;
+}
+int htn_heff0_apply(htn_mps* mps, int32_t b, const void* x_host, void* y_host) {
+    if (!mps || !x_host || !y_host) return set_error("htn_heff0_apply: bad arguments");
+    if (mps->bond0_checks(b, "htn_heff0_apply")) return 1;
+    if (mps->be->activate()) return 1;
+    auto ap = mps->make_apply0(b);
+    if (!ap) return 1;
+    return mps->apply_once(*ap, mps->Lbuf[b], mps->Rbuf[b], htn_mps_bond_size(mps, b), x_host, y_host, false);
+}
 int htn_mps_set_mpo(htn_mps* mps, const htn_mpo* mpo) {
     if (!mps || !mpo) return set_error("htn_mps_set_mpo: bad arguments");
     if (mps->be->activate()) return 1;

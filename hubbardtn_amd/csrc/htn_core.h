@@ -240,6 +240,12 @@ void plan_apply(const Mpo& mpo, const ThetaLayout& tl, const EnvLayout& Ll, cons
 // (2S_c' + 1) / (2S_c + 1) -- the centre carries sqrt(2S_r + 1) in both layout kinds, as theta does (coef_apply).
 // buffers: BUF_X in, BUF_Y out, BUF_L / BUF_R the environments of the site's bonds, BUF_Z the staging of terms that have both.
 void plan_apply1(const Mpo& mpo, const SiteLayout& lay, const EnvLayout& Ll, const EnvLayout& Rl, const MpoSite& W, ApplyPlan& out);
+// zero-site effective Hamiltonian y = GL . x . GR for the bond matrix between two sites (the backward step of one-site TDVP), in
+// BOND layout: one n_c x n_c matrix per sector c of `bond`, in its sector order, ld n_c -- the layout plan_gauge1 gives the
+// triangular factors when every sector of the bond is reached.  plan_apply1 with the site's MPO tensor removed: coef_left of a
+// j = 0 site under the identity (= 1) x (2S_c' + 1) / (2S_c + 1); the bond matrix carries sqrt(2S_c + 1) like the centre.
+// buffers: BUF_X in, BUF_Y out, BUF_L / BUF_R the two environments of the bond, BUF_Z the staging of the levels that have both.
+void plan_apply0(const Mpo& mpo, const Bond& bond, const EnvLayout& Ll, const EnvLayout& Rl, ApplyPlan& out);
 // gauge move of a one-site update: QR / LQ descriptors of the centre's sector matrices (left layout: QR, the centre moves
 // right; right layout: LQ, it moves left) and the absorption of the triangular factors (BUF_S1) into the neighbour (BUF_S2 -> BUF_Y)
 void plan_gauge1(const SiteLayout& cen, const SiteLayout& nb, std::vector<htn_qr_block>& desc, int64_t& rsize, Tasks& out);

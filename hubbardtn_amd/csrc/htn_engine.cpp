@@ -84,6 +84,14 @@ std::shared_ptr<ApplyC> htn_mps::make_apply1(int i, const SiteLayout& lay) {
         return compile_apply(p, false);
     });
 }
+// compiled zero-site H_eff apply of bond b (between sites b - 1 and b), in bond layout
+std::shared_ptr<ApplyC> htn_mps::make_apply0(int b) {
+    return cached<ApplyC>(ikey("apply0", b) + bonds[b]->key, [&]() -> std::shared_ptr<ApplyC> {
+        ApplyPlan p;
+        plan_apply0(*mpo, *bonds[b], *Llay[b], *Rlay[b], p);
+        return compile_apply(p, false);
+    });
+}
 
 // stage table of an apply between the environments L and R (the Z stage if the plan has one, then the Y stage), split-K
 // workspace ensured; the Lanczos driver fills in x and y.  -> number of stages, < 0 on error

@@ -311,10 +311,11 @@ struct htn_mps {
     int env_step(char side, int i);
     int left_env(int i) { return env_step('L', i); }
     int right_env(int i) { return env_step('R', i); }
-    // H_eff applies (two-site: make_apply, one-site: make_apply1)
+    // H_eff applies (two-site: make_apply, one-site: make_apply1, zero-site on a bond: make_apply0)
     std::shared_ptr<ApplyC> compile_apply(ApplyPlan& p, bool deal_y);
     std::shared_ptr<ApplyC> make_apply(int i, const ThetaLayout& tl);
     std::shared_ptr<ApplyC> make_apply1(int i, const SiteLayout& lay);
+    std::shared_ptr<ApplyC> make_apply0(int b);
     int apply_stages(const ApplyC& ap, const DView& L, const DView& R, const DView& z, htn_gemm_launch* stages);
     int apply_once(const ApplyC& ap, const DView& L, const DView& R, int64_t n, const void* x_host, void* y_host, bool exchange);
     int theta_into(int i, const ThetaLayout& tl, cplx* dst);
@@ -333,7 +334,7 @@ struct htn_mps {
     int sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
     int set_mpo(htn_mpo* m);
     // ---- htn_site.cpp: one-site DMRG (htn_site_update / htn_dmrg1_sweep) and time evolution (htn_bond_evolve /
-    // htn_site_evolve / htn_tdvp2_sweep) ----
+    // htn_site_evolve / htn_tdvp2_sweep; one-site TDVP: htn_site_evolve_move / htn_tdvp1_sweep) ----
     int relay(const SiteLayout& from, const cplx* src, const SiteLayout& to, cplx* dst);
     int site_solve(int i, const SiteLayout& from, const SiteLayout& lay, bool optimise, const cplx* evolve_dt, const htn_sweep_opts& o,
                    StageClock& clk, SiteWork& w);
@@ -342,6 +343,9 @@ struct htn_mps {
     int evolve_checks(const htn_sweep_opts& o, const char* who) const;
     int evolve_site(int i, cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* log_growth);
     int tdvp2_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* E, double* log_norm);
+    int bond0_checks(int b, const char* who) const;
+    int evolve_site_move(int i, int direction, cplx dt_fwd, cplx dt_back, const htn_sweep_opts& o, htn_bond_stats* st, double* log_growth);
+    int tdvp1_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* E, double* log_norm);
     // ---- htn_overlap.cpp: overlap environments, attached states, two-point correlation functions ----
     // overlap transfers with `ket` as the ket state (this = bra): in -> out across site i
     int ovl_step(char side, const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);

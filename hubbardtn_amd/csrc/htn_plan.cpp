@@ -932,6 +932,74 @@ void plan_apply1(const Mpo& mpo, const SiteLayout& lay, const EnvLayout& Ll, con
     out.nterms = nterms;
 }
 
+// ---- y = H_eff x for NO site (the bond matrix between two sites: the backward step of one-site TDVP) --------------------
+// y[c'] += coef * L[c',w,c] x[c] R[c,w,c'] over the MPO levels w of the bond: plan_apply1 with the site's MPO tensor removed,
+// i.e. a site of one multiplet (j = 0) under the identity (k = 0, reduced element 1), so that a = c, a' = c' and both levels
+// are w: coef = coef_left(j = 0 site) * (2S_c' + 1) / (2S_c + 1).  x and y are in BOND layout: one n_c x n_c matrix per sector
+// of the bond, in the bond's sector order, leading dimension n_c -- what plan_gauge1 lays out for the triangular factors.
+// Level 0 has no left environment, the last level no right one; every other level goes through BUF_Z (Z = L x), like plan_apply1.
+void plan_apply0(const Mpo& mpo, const Bond& bond, const EnvLayout& Ll, const EnvLayout& Rl, ApplyPlan& out) {
+    const Sym& sym = mpo.sym;
+    const std::vector<Lvl>& levels = Ll.levels;
+    const int nfin = (int)levels.size() - 1;
+    TaskList ty, tz;
+    std::vector<int64_t> offs(bond.secs.size());
+    int64_t size = 0;
+    for (size_t ci = 0; ci < bond.secs.size(); ++ci) {
+        const Sec c = bond.secs[ci];
+        const int n = bond.dims[ci];
+        offs[ci] = size;
+        ty.block(mk(c.N, c.j), BUF_Y, size, n, n, n);
+        size += (int64_t)n * n;
+    }
+    int64_t zoff = 0, nterms = 0;
+    for (size_t ci = 0; ci < bond.secs.size(); ++ci) {
+        const Sec c = bond.secs[ci];
+        const int nc = bond.dims[ci];
+        const int64_t xoff = offs[ci];
+        for (int w = 0; w <= nfin; ++w) {
+            const bool hasL = w != 0, hasR = w != nfin;
+            std::vector<Sec> one_c{c};
+            const std::vector<Sec>* cps = hasL ? Ll.kets(w, c) : (hasR ? Rl.kets(w, c) : &one_c);
+            if (!cps) continue;
+            const int kw = sym.jeff(levels[w].k);
+            for (Sec cp : *cps) {
+                const int oi = ty.find(mk(cp.N, cp.j));
+                if (oi < 0) continue;
+                const int lb = hasL ? Ll.block(cp, w, c) : 0, rb = hasR ? Rl.block(c, w, cp) : 0;
+                if (lb < 0 || rb < 0) continue;
+                const int jc = sym.jeff(c.j), jcp = sym.jeff(cp.j);
+                const double cf = coef_left(jcp, kw, jc, 0, 0, 0, jcp, kw, jc) * (jcp + 1) / (jc + 1);
+                const cplx alpha = cf;
+                if (alpha == cplx(0.0, 0.0)) continue;
+                ++nterms;
+                if (!hasL && !hasR) {
+                    ty.copy(oi, BUF_X, xoff, nc, alpha);
+                } else if (hasL && !hasR) {
+                    const auto& Lb = Ll.blocks[lb];
+                    ty.gemm(oi, BUF_L, Lb.off, Lb.m, HTN_OP_N, BUF_X, xoff, nc, HTN_OP_N, Lb.n, alpha);
+                } else if (hasR && !hasL) {
+                    const auto& Rb = Rl.blocks[rb];
+                    ty.gemm(oi, BUF_X, xoff, nc, HTN_OP_N, BUF_R, Rb.off, Rb.m, HTN_OP_N, Rb.m, alpha);
+                } else {
+                    const auto& Lb = Ll.blocks[lb];
+                    const auto& Rb = Rl.blocks[rb];
+                    const int zi = tz.block(mk(oi, w, c.N, c.j), BUF_Z, zoff, Lb.m, nc, Lb.m);
+                    ty.gemm(oi, BUF_Z, zoff, Lb.m, HTN_OP_N, BUF_R, Rb.off, Rb.m, HTN_OP_N, Rb.m, 1.0);
+                    tz.gemm(zi, BUF_L, Lb.off, Lb.m, HTN_OP_N, BUF_X, xoff, nc, HTN_OP_N, Lb.n, alpha);
+                    zoff += (int64_t)Lb.m * nc;
+                }
+            }
+        }
+    }
+    out.has_z = zoff > 0;
+    if (out.has_z) tz.finalize(out.tz);
+    ty.finalize(out.ty);
+    out.ty.group_bounds = offs;                                                // placement hint: one group per sector matrix of y
+    out.zsize = zoff;
+    out.nterms = nterms;
+}
+
 // ---- gauge move of a one-site update -----------------------------------------------------------------------------------
 // QR (centre in left layout, move right) or LQ (right layout, move left) descriptors of the centre's sector matrices, and
 // the task list that takes the triangular factors (BUF_S1, one n_c x n_c matrix per sector, ld n_c) into the neighbour

@@ -1,5 +1,6 @@
 // One-site updates and time evolution of an htn_mps (htn_engine.h): htn_site_update / htn_dmrg1_sweep, and htn_site_evolve /
-// htn_tdvp2_sweep, whose backward step is the same one-site solve under an exponential.  Host C++ (no HIP).
+// htn_tdvp2_sweep, whose backward step is the same one-site solve under an exponential, and htn_site_evolve_move /
+// htn_tdvp1_sweep, one-site TDVP, whose backward step is a zero-site solve on the bond.  Host C++ (no HIP).
 // NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
 #include "htn_engine.h"
 
@@ -197,6 +198,118 @@ int htn_mps::tdvp2_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, d
         if (bond(i, +1, true, i < L - 2 ? i + 1 : -1)) return 1;
     for (int i = L - 2; i >= 0; --i)
         if (bond(i, -1, false, i > 0 ? i : -1)) return 1;
+    if (E) *E = energy;
+    if (log_norm) *log_norm = lg;
+    return 0;
+}
+
+// =====================================================================================================================
+// Time evolution at fixed bond tables: one-site TDVP (htn_site_evolve_move / htn_tdvp1_sweep).  A move is
+// the one-site exponential of evolve_site, the QR / LQ gauge move of update_site, and -- before the triangular factor C goes
+// into the neighbour -- the backward step C <- exp(-i dt_back H_eff0) C on the bond, H_eff0 = GL_b . GR_b with the left
+// environment that already holds the new isometry (plan_apply0).  C is the Krylov row 0 of that solve where the QR wrote it.
+// =====================================================================================================================
+// what the zero-site apply of bond b asks of the state: the centre next to the bond, both environments on the bond's table
+int htn_mps::bond0_checks(int b, const char* who) const {
+    if (b < 1 || b >= L) return set_error("%s: bond %d out of range (1..%d)", who, b, L - 1);
+    if (centre != b - 1 && centre != b) return set_error("%s: the centre is on site %d, not next to bond %d", who, centre, b);
+    if (!Llay[b] || !Rlay[b] || Llay[b]->bond->key != bonds[b]->key || Rlay[b]->bond->key != bonds[b]->key)
+        return set_error("%s: bond %d does not have both environments on its bond table", who, b);
+    return 0;
+}
+
+int htn_mps::evolve_site_move(int i, int direction, cplx dt_fwd, cplx dt_back, const htn_sweep_opts& o, htn_bond_stats* st,
+                              double* log_growth) {
+    const char* who = "htn_site_evolve_move";
+    if (evolve_checks(o, who) || site1_checks(this, i, who)) return 1;
+    if (direction != -1 && direction != 1) return set_error("%s: direction %d (must be -1 or +1)", who, direction);
+    if ((direction > 0 && i + 1 >= L) || (direction < 0 && i == 0)) return set_error("%s: site %d has no neighbour in direction %d", who, i, direction);
+    StageClock clk(be, o.profile);
+    const SiteLayoutP cur = site_lay[i];
+    const SiteLayoutP lay = site_layout(direction > 0 ? 'L' : 'R', bonds[i], bonds[i + 1]);
+    if (lay->size <= 0) return set_error("%s: empty site tensor on site %d", who, i);
+    for (const auto& M : lay->mats)      // a full-rank gauge move needs the long side along the orthonormal direction
+        if (lay->kind == 'L' ? M.rows < M.cols : M.cols < M.rows)
+            return set_error("%s: sector (%d, %d) of site %d is a %d x %d block, its bond is wider than the rest of the "
+                             "site supports: run a two-site sweep first", who, M.c.N, M.c.j, i, M.rows, M.cols);
+    const int j = i + direction, b = direction > 0 ? i + 1 : i;
+    const SiteLayoutP nl = site_lay[j];
+    if (nl->kind != (direction > 0 ? 'R' : 'L')) return set_error("%s: site %d is not in %s layout", who, j, direction > 0 ? "right" : "left");
+    auto gc = cached<Gauge1C>(std::string(direction > 0 ? "gauge1R" : "gauge1L") + lay->bl->key + "|" + lay->br->key + "|" +
+                                  (direction > 0 ? nl->br->key : nl->bl->key),
+                              [&]() -> std::shared_ptr<Gauge1C> {
+                                  auto g = std::make_shared<Gauge1C>();
+                                  Tasks t;
+                                  plan_gauge1(*lay, *nl, g->desc, g->rsize, t);
+                                  if (!(g->desc_dev = upload_vec(be, g->desc)) || upload_tasks(t, g->absorb)) return nullptr;
+                                  return g;
+                              });
+    if (!gc) return 1;
+    // the triangular factors are in bond layout only if the site reaches every sector of the bond (any state a two-site sweep shaped)
+    int64_t n0 = 0;
+    for (int d : bonds[b]->dims) n0 += (int64_t)d * d;
+    if (gc->desc.size() != bonds[b]->secs.size() || gc->rsize != n0)
+        return set_error("%s: site %d does not reach every sector of bond %d: run a two-site sweep first", who, i, b);
+    // ---- forward step on the site ----
+    SiteWork w;
+    if (site_solve(i, *cur, *lay, true, &dt_fwd, o, clk, w)) return 1;             // (laps clk.plan and clk.lanczos)
+    const Solve& s = w.sol;
+    // ---- gauge move: Q stays on the site, C = R (or L) is row 0 of the bond's Krylov basis ----
+    const int kd = o.krylovdim;
+    DView V0 = zalloc((int64_t)(kd + 2) * n0, false), nb_out = zalloc(nl->size, false);
+    if (!V0.base || !nb_out.base) return set_error("device allocation failed (gauge move)");
+    if (be->qr_blocks(w.out.ptr(), V0.ptr(), (const htn_qr_block*)gc->desc_dev->p, gc->desc.data(), (int)gc->desc.size())) return 1;
+    site_lay[i] = lay;
+    site_buf[i] = w.out;
+    clk.lap();                           // (the QR / LQ and, below, the absorption: t_svd is what the other stages leave of the total)
+    if (direction > 0 ? left_env(i) : right_env(i)) return 1;
+    clk.env = clk.lap();
+    // ---- backward step on the bond ----
+    Solve s0;
+    s0.n = n0;
+    s0.ap = make_apply0(b);
+    if (!s0.ap) return 1;
+    DView z0 = zalloc(s0.ap->zsize, false);
+    if (!z0.base) return set_error("device allocation failed (zero-site apply)");
+    htn_gemm_launch stages[2];
+    const int ns = apply_stages(*s0.ap, Lbuf[b], Rbuf[b], z0, stages);
+    if (ns < 0) return 1;
+    if (be->krylov_expm(stages, ns, BUF_X, BUF_Y, V0.ptr(), n0, kd, dt_back.real(), dt_back.imag(), o.lanczos_tol, o.maxrestart, 0, nullptr,
+                        ctx, &s0.growth, &s0.E, &s0.nmv, &s0.res, be->timing ? &s0.mv_ms : nullptr))
+        return 1;
+    clk.lanczos += clk.lap();
+    // ---- the evolved C goes into the neighbour, which becomes the centre ----
+    if (gemm(gc->absorb, {{BUF_S1, V0.ptr()}, {BUF_S2, site_buf[j].ptr()}, {BUF_Y, nb_out.ptr()}})) return 1;
+    site_buf[j] = nb_out;
+    centre = j;
+    energy = s.E;
+    norm_absorbed();
+    if (log_growth) *log_growth += log(s.growth) + log(s0.growth);
+    if (st) {
+        fill_stats(st, b, direction, s, Llay[i]->size + Rlay[i + 1]->size, 0, 0, 0.0, clk);
+        st->n_matvec += s0.nmv;
+    }
+    return 0;
+}
+
+int htn_mps::tdvp1_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* E, double* log_norm) {
+    if (evolve_checks(o, "htn_tdvp1_sweep")) return 1;
+    if (L < 2) return set_error("htn_tdvp1_sweep: a chain of %d site(s) has no bond to sweep over", L);
+    if (centre != 0) return set_error("htn_tdvp1_sweep: the centre is on site %d, not on site 0", centre);
+    const cplx half = 0.5 * dt, back = -0.5 * dt;
+    double lg = 0.0;
+    int k = 0;
+    for (int i = 0; i < L - 1; ++i, ++k)
+        if (evolve_site_move(i, +1, half, back, o, st ? st + k : nullptr, &lg)) return 1;
+    for (int i = L - 1; i >= 1; --i, ++k)          // (site L-1: its two forward half steps as one solve of length dt)
+        if (evolve_site_move(i, -1, i == L - 1 ? dt : half, back, o, st ? st + k : nullptr, &lg)) return 1;
+    htn_bond_stats site_st;
+    if (evolve_site(0, half, o, &site_st, &lg)) return 1;
+    energy = site_st.energy;
+    if (st) {
+        htn_bond_stats* rec = st + k - 1;
+        rec->n_matvec += site_st.n_matvec, rec->t_total += site_st.t_total, rec->t_lanczos += site_st.t_lanczos;
+    }
     if (E) *E = energy;
     if (log_norm) *log_norm = lg;
     return 0;

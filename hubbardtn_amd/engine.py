@@ -505,6 +505,59 @@ class DMRG2:
         self.log_norm = lg.value
         return self.energy
 
+    # ---- time evolution at fixed bond tables: one-site TDVP (htn_site_evolve_move / htn_tdvp1_sweep / htn_heff0_apply) ----
+    def evolve_site_move(self, i, direction, dt_fwd, dt_back, record=True):
+        """one move of one-site TDVP (the centre must be on site i): site <- exp(-i dt_fwd H_eff1) site, QR (direction +1) or
+        LQ (-1) as update_site, the triangular factor C <- exp(-i dt_back H_eff0) C on the bond crossed, C into the neighbour,
+        which becomes the centre.  Bond tables never change.  -> BondStats (energy = <psi|H|psi> before the move)"""
+        self.__dict__.pop("_bond_cache", None)
+        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
+        o, f, b = self._opts(), complex(dt_fwd), complex(dt_back)
+        self._check(self.lib.htn_site_evolve_move(self.handle, i, direction, f.real, f.imag, b.real, b.imag, C.byref(o),
+                                                  st.ctypes.data), "htn_site_evolve_move")
+        s = _stats(st[0])
+        if record:
+            self.stats.append(s)
+            self.energy = s.energy
+        return s
+
+    def tdvp1_sweep(self, dt):
+        """one symmetric one-site TDVP step of length dt (complex; -i beta: imaginary time) at the current bond tables, one
+        library call: evolve_site_move(i, +1, dt/2, -dt/2) rightwards, the last site by dt, the mirror image leftwards, site 0
+        by dt/2 (2L-2 records, trunc_weight 0: nothing is truncated).  The centre starts and ends on site 0, the state stays
+        normalised and `log_norm` holds the logarithm of the norm change (0 for real dt).  Grow the bonds with sweep() or
+        tdvp_sweep() first; the Schmidt spectra (`spectrum`) keep the values of the last two-site update of each bond.
+        Returns <psi|H|psi> as the closing step on site 0 saw it."""
+        self.__dict__.pop("_bond_cache", None)
+        n = 2 * self.L - 2
+        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
+        E, lg = C.c_double(0.0), C.c_double(0.0)
+        o, dt = self._opts(), complex(dt)
+        self._check(self.lib.htn_tdvp1_sweep(self.handle, dt.real, dt.imag, C.byref(o), st.ctypes.data, C.byref(E), C.byref(lg)),
+                    "htn_tdvp1_sweep")
+        self.stats.extend(_stats(r) for r in st)
+        self.energy = E.value
+        self.log_norm = lg.value
+        return self.energy
+
+    def bond_size(self, b) -> int:
+        """elements of a vector in bond layout on bond b: one n_c x n_c column-major matrix per sector, in the order of
+        `bonds[b]` (the layout of the triangular factors of a gauge move)"""
+        n = int(self.lib.htn_mps_bond_size(self.handle, b))
+        if n < 0:
+            raise ValueError(f"bond_size: bond {b} out of range")
+        return n
+
+    def apply_heff0(self, b, x):
+        """y = H_eff0(bond b) x on host vectors in bond layout (bond_size(b)); the centre must be on site b - 1 or b with both
+        environments of the bond present, as after a gauge move across it"""
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        n = self.bond_size(b)
+        assert x.shape == (n,)
+        y = np.zeros(n, dtype=np.complex128)
+        self._check(self.lib.htn_heff0_apply(self.handle, b, x.ctypes.data, y.ctypes.data), "htn_heff0_apply")
+        return y
+
     def set_mpo(self, mpo):
         """swap the Hamiltonian under the state (a quench): same symmetry, chain length and site multiplets, centre on site
         0.  The environments are rebuilt on the device; the tensors are not touched."""

@@ -568,6 +568,34 @@ int htn_tdvp2_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_op
                     double* energy_host, double* log_norm_host);
 int htn_mps_set_mpo(htn_mps* mps, const htn_mpo* mpo);
 
+/* Time evolution at FIXED bond tables: one-site TDVP (Haegeman et al., as above; MPSKit's TDVP() beside TDVP2()).  Nothing is
+ * truncated: the norm and, for real dt, the energy are conserved to the tolerance of the Krylov solves and a step is exactly
+ * reversible; the bond tables and the Schmidt spectra of htn_mps_spectrum stay as the last two-site update left them.
+ * htn_site_evolve_move: the centre must be on site i.  site <- exp(-i fwd H_eff1) site (the solve of htn_site_evolve, in left
+ *   layout for direction +1, right layout for -1), then the QR / LQ of htn_site_update: Q stays on site i, the environment moves
+ *   across it, and the triangular factor C is evolved by exp(-i back H_eff0) on the bond it sits on -- H_eff0(C) = sum_w GL_w C
+ *   GR_w with the environment that already holds Q (htn_heff0_apply) -- before it is absorbed into the neighbour, the new centre.
+ *   direction 0 is refused (htn_site_evolve is that call).  stats (may be NULL): bond = the bond crossed, energy = the first
+ *   Lanczos alpha of the site solve (<psi|H|psi> before the move), residual = its error estimate, n_matvec = site + bond
+ *   matvecs, n_tiles / theta_size / apply_flops of the site apply, jacobi_sweeps = trunc_weight = 0.
+ * htn_tdvp1_sweep: one symmetric second-order step of length dt.  Rightwards i = 0 .. L-2: site_evolve_move(i, +1, dt/2, -dt/2);
+ *   leftwards i = L-1 .. 1: site_evolve_move(i, -1, dt/2, -dt/2), where site L-1 takes its two forward half steps as one solve
+ *   of length dt; then site_evolve(0, dt/2).  The centre must be on site 0 (else an error, the state untouched) and ends there.
+ *   stats_host: 2L-2 records or NULL (the last one includes the closing step on site 0); energy_host = the first alpha of that
+ *   closing step; log_norm_host as for htn_tdvp2_sweep.
+ * Refused: what htn_site_update and htn_tdvp2_sweep refuse (communicator or exchange hook, attached states, iDMRG windows,
+ * krylovdim outside 2..31, a sector block with fewer rows than columns: "run a two-site sweep first").
+ * htn_mps_bond_size: elements of a vector in BOND layout on bond b (0..L) -- one n_c x n_c column-major matrix per sector c of
+ *   the bond, in the order of htn_mps_bond: the layout of the triangular factors of a gauge move.
+ * htn_heff0_apply: y = H_eff0(bond b) x on host vectors in bond layout; 1 <= b <= L-1, the centre on site b-1 or b and both
+ *   environments of bond b present on its table (after a gauge move across b they are).  Tests and Hermiticity checks. */
+int htn_site_evolve_move(htn_mps* mps, int32_t i, int32_t direction, double fwd_re, double fwd_im, double back_re, double back_im,
+                         const htn_sweep_opts* opts, htn_bond_stats* stats_host);
+int htn_tdvp1_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_opts* opts, htn_bond_stats* stats_host,
+                    double* energy_host, double* log_norm_host);
+int64_t htn_mps_bond_size(htn_mps* mps, int32_t b);
+int htn_heff0_apply(htn_mps* mps, int32_t b, const void* x_host, void* y_host);
+
 /* Excited states inside one sector: orthogonalised two-site DMRG.  After htn_mps_set_orthogonal(mps, others, n) every
  * OPTIMISING bond update of `mps` finds the lowest eigenpair of H_eff inside the orthogonal complement of the n attached
  * states: per attached state phi_k the overlap environments <mps|phi_k> of every bond are built at the call and moved with

@@ -314,6 +314,49 @@ end
 # In compute_groundstate (src/HubbardFunctions.jl:1010) a finite-chain run then reads
 #     ψ, envs, δ = find_groundstate(ψ₀, H, HubbardHIP.HIPDMRG2(; trscheme = truncbelow(10.0^(-svalue)), tol = tol, P = P, Q = Q))
 
+# ---- time evolution at fixed bond tables: one-site TDVP (htn_tdvp1_sweep; MPSKit.TDVP's role) -----------------------------
+# UNTESTED like everything in this file.  Nothing is truncated: ψ keeps the bond tables it arrives with (grow them first, with
+# HIPDMRG2 or with MPSKit's own TDVP2).  A two-site binding would differ only in the entry point (htn_tdvp2_sweep) and in the
+# trscheme handed to sweep_opts; it is not written yet.
+struct HIPTDVP <: MPSKit.Algorithm
+    tol::Float64
+    krylovdim::Int
+    maxrestart::Int
+    P::Int
+    Q::Int
+end
+HIPTDVP(; tol = 1e-10, krylovdim = 30, maxrestart = 8, P = 1, Q = 1) = HIPTDVP(tol, krylovdim, maxrestart, P, Q)
+
+# ψ(t + dt) = exp(-i dt H) ψ(t) by one symmetric one-site sweep; dt complex (-i β: imaginary time, ψ stays normalised).
+# The state is uploaded and downloaded per call: a caller who takes many steps keeps the htn_mps handle instead (the loop below
+# the upload is all a longer run needs).
+function MPSKit.timestep(ψ::FiniteMPS, H, t::Number, dt::Number, alg::HIPTDVP, envs = nothing)
+    ctx, mpo, mps = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:htn_ctx_create, lib), Cint, (Int32, Int32, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), 1, 0, C_NULL, ctx))
+    try
+        sym, ops, level_ptr, levels, entry_ptr, entries = export_mpo(H, alg.P, alg.Q)
+        check(ccall((:htn_mpo_create, lib), Cint,
+            (Ptr{Cvoid}, Ref{HtnSymmetry}, Int32, Ptr{HtnSiteOp}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{HtnMpoEntry}, Ref{Ptr{Cvoid}}),
+            ctx[], sym, length(H), ops, length(ops), level_ptr, levels, entry_ptr, entries, mpo))
+        bond_ptr, sectors_, sub_ptr, subs, data_ptr, data = export_mps(ψ, alg.P, alg.Q)
+        check(ccall((:htn_mps_create, lib), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{HtnSector}, Ptr{Int32}, Ptr{HtnSubblock}, Ptr{Int64}, Ptr{ComplexF64},
+             Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+            ctx[], mpo[], length(ψ), bond_ptr, sectors_, sub_ptr, subs, data_ptr, data, C_NULL, C_NULL, mps))
+        opts = sweep_opts(TensorKit.NoTruncation(); krylovdim = alg.krylovdim, tol = alg.tol, maxrestart = alg.maxrestart)
+        E, lognorm = Ref{Float64}(0.0), Ref{Float64}(0.0)
+        z = ComplexF64(dt)
+        check(ccall((:htn_tdvp1_sweep, lib), Cint, (Ptr{Cvoid}, Float64, Float64, Ref{HtnSweepOpts}, Ptr{Cvoid}, Ref{Float64}, Ref{Float64}),
+            mps[], real(z), imag(z), opts, C_NULL, E, lognorm))
+        ψ′ = import_mps(mps[], ψ, alg.P, alg.Q)
+        return ψ′, environments(ψ′, H)
+    finally
+        mps[] == C_NULL || ccall((:htn_mps_destroy, lib), Cvoid, (Ptr{Cvoid},), mps[])
+        mpo[] == C_NULL || ccall((:htn_mpo_destroy, lib), Cvoid, (Ptr{Cvoid},), mpo[])
+        ccall((:htn_ctx_destroy, lib), Cvoid, (Ptr{Cvoid},), ctx[])
+    end
+end
+
 # ---- infinite chain: the library's IDMRG2 driver (htn_idmrg_*) ------------------------------------------------------------
 # UNTESTED like everything in this file (no Julia in the build image).  The same protocol is exercised from Python by
 # tests/test_idmrg_native_cpu.py (C ABI only) and hubbardtn_amd/idmrg.py (_native_idmrg2).
