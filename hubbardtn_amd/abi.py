@@ -135,7 +135,7 @@ assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(Idmr
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
            "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z",
-           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z", "htn_block_place_z"]
+           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z", "htn_block_place_z", "htn_krylov_combine2_z"]
 # entry points shared by libhubbardtn_hip.so and the CPU baseline library (oracle/cpu_backend)
 ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_ctx_set_timing", "htn_comm_unique_id",
                   "htn_ctx_set_comm", "htn_ctx_set_exchange", "htn_mpo_create", "htn_mpo_destroy", "htn_mps_create",
@@ -149,7 +149,8 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_qr_blocks_z", "htn_mps_correlator",
                   "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo",
                   "htn_mps_apply_op", "htn_mps_transition", "htn_block_nullproj_z", "htn_mps_variance",
-                  "htn_site_evolve_move", "htn_tdvp1_sweep", "htn_mps_bond_size", "htn_heff0_apply"]
+                  "htn_site_evolve_move", "htn_tdvp1_sweep", "htn_mps_bond_size", "htn_heff0_apply",
+                  "htn_krylov_solve_z", "htn_bond_solve", "htn_cv_sweep"]
 
 
 class GemmLaunch(C.Structure):
@@ -204,6 +205,7 @@ def load_library(path: str | None = None):
     lib.htn_block_trdots_z.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
     lib.htn_krylov_combine_z.argtypes = [vp, i64, i32, vp, i64, vp]
     lib.htn_block_place_z.argtypes = [vp, vp, vp, i32, vp]
+    lib.htn_krylov_combine2_z.argtypes = [vp, i64, i32, vp, vp, vp, i32, i64, vp]
     declare_engine(lib)
     for name in EXPORTS + ENGINE_EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
@@ -291,6 +293,10 @@ def declare_engine(lib):
     lib.htn_mps_bond_size.argtypes = [vp, i32]
     lib.htn_mps_bond_size.restype = i64
     lib.htn_heff0_apply.argtypes = [vp, i32, vp, vp]
+    lib.htn_krylov_solve_z.argtypes = [C.POINTER(GemmLaunch), i32, i32, i32, vp, i64, i32, f64, f64, f64, i32, vp, i32, vp, i32,
+                                       EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i32), C.POINTER(f64), vp]
+    lib.htn_bond_solve.argtypes = [vp, i32, i32, i32, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
+    lib.htn_cv_sweep.argtypes = [vp, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

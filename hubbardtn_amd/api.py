@@ -100,6 +100,19 @@ class TDVP:
 
 
 @dataclass
+class CorrectionVector:
+    """correction-vector (DDMRG) selector: trscheme truncates every bond step, tol is the relative residual of the local solves
+    (krylovdim vectors per cycle, at most maxrestart restarts), sweeps per frequency run until <b|x> changes by less than
+    sweep_tol relative, at most maxsweeps"""
+    trscheme: object = None
+    krylovdim: int = 30
+    tol: float = 1e-8
+    maxrestart: int = 50
+    sweep_tol: float = 1e-6
+    maxsweeps: int = 10
+
+
+@dataclass
 class InfiniteHamiltonian:
     """the model of a translation-invariant chain; len() = sites per unit cell (length(H) in the reference)"""
     simul: Simulation
@@ -717,6 +730,82 @@ def spectral_function(res, q, omegas, eta):
     if not np.ndim(omegas):
         A = A[..., 0]
     return A
+
+
+def correction_vector(psi0, H, omegas, eta, alg, op="c+", site=None, part="particle"):
+    """frequency-space Green's function by correction-vector sweeps:
+    G[w, x] = <O_x psi0| (omega + i eta -+ (H - E0))^-1 O_site psi0> for all sites x and every omega of `omegas`, eta > 0 the
+    Lorentzian broadening, E0 = <psi0|H|psi0>, site = L // 2 by default.  part = "particle" (sign -, op normally "c+"): the
+    solve is (z - H) x = b with z = E0 + omega + i eta; part = "hole" (sign +, op normally "c"): z = E0 - omega - i eta and the
+    overall sign flips.  b = O_site psi0 (apply_operator), x an MPS of its own: per omega `cv_sweep`s (engine.DMRG2) until
+    |delta <b|x>| <= sweep_tol |<b|x>| or alg.maxsweeps, then G[w] = psi0.engine.transition(op, x) -- the amplitude of x (the
+    norm of the solution; the stored tensors stay normalised) is applied inside the library, as for every applied state.  The
+    next omega starts from the previous x.  As for greens_function the overlaps carry the sum over the components of the
+    operator's multiplet.  Resolution is eta by construction and no time evolution is involved; real z (eta = 0) is not
+    guaranteed to converge.  -> {"omegas", "G": [len(omegas), L] complex, "E0", "sweeps" (per omega), "residual" (largest relative
+    residual of the last sweep's solves), "trunc_weight" (largest discarded weight of the last sweep), "site", "eta"}"""
+    if isinstance(psi0, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
+        raise NotImplementedError("correction_vector needs a chain length: it is solved on a finite chain, not on an InfiniteMPS")
+    if not isinstance(alg, CorrectionVector):
+        raise TypeError("correction_vector takes alg = CorrectionVector(...)")
+    if part not in ("particle", "hole"):
+        raise ValueError("part must be 'particle' or 'hole'")
+    L = psi0.L
+    site = L // 2 if site is None else int(site)
+    omegas = [float(w) for w in np.atleast_1d(omegas)]
+    eta = float(eta)
+    b = apply_operator(psi0, op, site)
+    b.engine.move_centre(0)             # (its norm now sits beside normalised tensors: the amplitude of b)
+    ref = psi0.engine.copy()            # (bond_energies moves the centre through the chain: not on the caller's state)
+    if H is not None and H is not ref.mpo and H is not ref.cmpo:
+        ref.set_mpo(H)
+        b.engine.set_mpo(H)
+    E0, _ = ref.bond_energies()
+    x = b.engine.copy()                 # start value: b itself, normalised
+    if isinstance(alg.trscheme, truncdim):
+        x.chi_full, x.cutoff = int(alg.trscheme.D), 0.0
+    elif isinstance(alg.trscheme, truncbelow):
+        x.chi_full, x.cutoff = None, float(alg.trscheme.eta)
+    elif alg.trscheme is None:
+        x.chi_full, x.cutoff = None, 0.0
+    else:
+        raise TypeError("trscheme must be truncdim(D) or truncbelow(eta)")
+    x.krylovdim, x.lanczos_tol, x.maxrestart = int(alg.krylovdim), float(alg.tol), int(alg.maxrestart)
+    x.set_orthogonal([b.engine])
+    sign = 1.0 if part == "particle" else -1.0
+    G = np.zeros((len(omegas), L), dtype=np.complex128)
+    sweeps = np.zeros(len(omegas), dtype=int)
+    resid, tw = np.zeros(len(omegas)), np.zeros(len(omegas))
+    try:
+        for k, w in enumerate(omegas):
+            z = E0 + sign * (w + 1j * eta)
+            last = None
+            for it in range(max(int(alg.maxsweeps), 1)):
+                k0 = len(x.stats)
+                bx, _ = x.cv_sweep(z)
+                sweeps[k] = it + 1
+                if last is not None and abs(bx - last) <= alg.sweep_tol * abs(bx):
+                    break
+                last = bx
+            resid[k] = max(s.residual for s in x.stats[k0:])
+            tw[k] = max(s.trunc_weight for s in x.stats[k0:])
+            G[k] = sign * psi0.engine.transition(op, x)
+    finally:
+        x.set_orthogonal([])
+    return {"omegas": np.array(omegas), "G": G, "E0": E0, "sweeps": sweeps, "residual": resid, "trunc_weight": tw, "site": site,
+            "eta": eta}
+
+
+def spectral_function_cv(res, q):
+    """A(q, omega) = -Im sum_x exp(-i q (x - site)) G[w, x] / pi from a correction_vector result; q (radians per site) a scalar
+    or an array -> array [len(q), len(omegas)] (a scalar q is squeezed out).  As for spectral_function, an open chain has no
+    momentum eigenstates: this is the Fourier transform in the distance from `site`."""
+    G = np.asarray(res["G"])
+    L = G.shape[1]
+    qs = np.atleast_1d(np.asarray(q, dtype=float))
+    ph = np.exp(-1j * qs[:, None] * (np.arange(L) - res["site"])[None, :])        # [q, x]
+    A = -(ph @ G.T).imag / np.pi
+    return A if np.ndim(q) else A[0]
 
 
 # ---- energy variance and extrapolation ---------------------------------------------------------------------------------

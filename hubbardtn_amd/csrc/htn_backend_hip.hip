@@ -272,6 +272,25 @@ struct HipBackend : htn::Backend {
         *n_matvec = nmv;
         return rc;
     }
+    int krylov_solve(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim, double z_re,
+                     double z_im, double tol, int max_restart, void* X, int use_guess, int zero_y, htn_exchange2_fn exchange, void* user,
+                     double* norm, double* residual, int* n_matvec, double* matvec_ms) override {
+        if (krylovdim < 2 || krylovdim > 31) return htn::set_error("krylov_solve: krylovdim must be in 2..31");
+        if (ensure_lan_scratch(htn_lanczos_scratch_elems(krylovdim))) return 1;
+        int32_t nmv = 0;
+        const int rc = htn_krylov_solve_z(stages, n_stages, x_slot, y_slot, V, n, krylovdim, z_re, z_im, tol, max_restart, X, use_guess,
+                                          lan_scratch, zero_y, exchange, user, norm, residual, &nmv, matvec_ms, st);
+        *n_matvec = nmv;
+        return rc;
+    }
+    // <a|b> by the dots kernels (one row), 16 bytes downloaded
+    int dotc(const void* a, const void* b, int64_t n, double* out_host) override {
+        if (ensure_lan_scratch(htn_dots_scratch_elems(32) + 64)) return 1;
+        double2* part = (double2*)lan_scratch;
+        double2* out = part + htn_dots_scratch_elems(32);
+        if (htn_dots_z(a, n, 1, b, n, out, part, st)) return 1;
+        return download(out_host, out, 2 * sizeof(double));
+    }
     // Gram-Schmidt of the projector rows on the device (htn_dots_z / htn_axpys_z, two passes per row); the host sees two
     // squared norms per row and decides whether the row stays
     int orthonormalise_rows(void* Pv, int64_t n, int nvec, double drop_tol, int* kept) override {

@@ -1,5 +1,5 @@
 // Host statements of the htn::Backend methods that are not pure (htn_core.h), and of the two kernel-level entries that have
-// one (htn_krylov_expm_z, htn_qr_blocks_z, htn_block_nullproj_z): vectors downloaded, H applied through the backend's grouped_gemm, the arithmetic
+// one (htn_krylov_expm_z, htn_krylov_solve_z, htn_qr_blocks_z, htn_block_nullproj_z): vectors downloaded, H applied through the backend's grouped_gemm, the arithmetic
 // in plain C++.  The CPU baseline library runs them; the HIP backend overrides every one with its kernels.  Nothing here
 // uses the sweep engine's types.  Host C++ (no HIP).
 // NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
@@ -9,6 +9,7 @@
 
 #include "htn_core.h"
 #include "htn_expm.h"
+#include "htn_resolvent.h"
 #include "htn_tridiag.h"
 
 using namespace htn;
@@ -181,6 +182,75 @@ int Backend::krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot
     *n_matvec = K.n_matvec;
     *err = ex.err_total;
     if (matvec_ms) *matvec_ms = 0.0;
+    return 0;
+}
+
+// (z - H) x = b, host statement (htn_core.h): the Lanczos basis with full two-pass reorthogonalisation on host copies of the
+// vectors, H through grouped_gemm, the stopping / restart decisions of htn_resolvent::Resolvent -- the ones the device driver takes
+int Backend::krylov_solve(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* Vv, int64_t n, int kd, double z_re,
+                          double z_im, double tol, int max_restart, void* Xv, int use_guess, int zero_y, htn_exchange2_fn exchange,
+                          void* user, double* norm, double* residual, int* n_matvec, double* matvec_ms) {
+    if (kd < 2 || kd > 31) return set_error("krylov_solve: krylovdim must be in 2..31");
+    if (!Vv || !Xv || n <= 0) return set_error("krylov_solve: bad arguments");
+    HostKrylov K{this, "krylov_solve", stages, n_stages, x_slot, y_slot, (cplx*)Vv, n, kd, zero_y, exchange, user};
+    if (download(K.B.data(), K.Vd, K.bytes)) return 1;
+    htn_resolvent::Resolvent rs;
+    rs.z = cplx(z_re, z_im), rs.tol = tol;
+    rs.bnorm = sqrt(hdot(K.row(0), K.row(0), n).real());
+    if (!(rs.bnorm > 0.0)) return set_error("krylov_solve: the right-hand side is zero or not finite");
+    std::vector<cplx> X((size_t)n, cplx(0.0, 0.0));
+    if (use_guess) {              // r0 = b - z x0 + H x0
+        if (download(X.data(), Xv, K.bytes)) return 1;
+        cplx *r = K.row(0), *hx = K.row(1);
+        if (K.matvec(X.data(), hx)) return 1;
+        ++K.n_matvec;
+        for (int64_t e = 0; e < n; ++e) r[e] += hx[e] - rs.z * X[(size_t)e];
+    }
+    double rnorm = sqrt(hdot(K.row(0), K.row(0), n).real());
+    if (!(rnorm == rnorm)) return set_error("krylov_solve: NaN in the residual of the start value");
+    rs.begin_cycle(rnorm);
+    if (rs.converged && !use_guess) return set_error("krylov_solve: tol >= 1 accepts x = 0");
+    const std::vector<const cplx*> none;
+    for (int restart = 0; !rs.converged; ++restart) {
+        for (int64_t e = 0; e < n; ++e) K.B[(size_t)e] *= 1.0 / rnorm;
+        double alpha = 0.0, beta = 0.0;
+        for (int j = 0; j < kd; ++j) {
+            if (K.extend(none, j, &alpha, &beta)) return 1;
+            if (rs.step(alpha, beta, kd)) break;
+            K.accept(j, beta);
+        }
+        if (!rs.converged && restart >= max_restart)
+            return set_error("krylov_solve: not converged after %d restart(s) of krylovdim %d: relative residual %.3e remains (tol %.3e)",
+                             std::max(max_restart, 0), kd, rs.resid, tol);
+        rs.finish();
+        K.combine(rs.y);
+        for (int64_t e = 0; e < n; ++e) X[(size_t)e] += K.x[(size_t)e];
+        if (rs.converged) break;
+        rnorm = rs.rho_norm();
+        if (!(rnorm > 0.0) || !(beta > 0.0)) return set_error("krylov_solve: the residual of an unconverged cycle vanished");
+        std::vector<cplx> c = rs.rho;                  // (the newest row is still the raw vector beta_m v_m)
+        for (cplx& v : c) v /= rnorm;
+        c.back() /= beta;
+        K.combine(c);
+        K.restart_from_x();
+        rnorm = 1.0;                                   // (row 0 is a unit vector already; beta_0 of the next cycle is |rho|)
+        rs.begin_cycle(rs.rho_norm());
+    }
+    const double xn = sqrt(hdot(X.data(), X.data(), n).real());
+    for (int64_t e = 0; e < n; ++e) K.B[(size_t)e] = xn > 0.0 ? X[(size_t)e] / xn : cplx(0.0, 0.0);
+    if (upload(Xv, X.data(), K.bytes) || K.finish()) return 1;
+    *norm = xn;
+    *residual = rs.resid;
+    *n_matvec = K.n_matvec;
+    if (matvec_ms) *matvec_ms = 0.0;
+    return 0;
+}
+
+int Backend::dotc(const void* a, const void* b, int64_t n, double* out_host) {
+    std::vector<cplx> ha((size_t)n), hb((size_t)n);
+    if (download(ha.data(), a, sizeof(cplx) * (size_t)n) || download(hb.data(), b, sizeof(cplx) * (size_t)n)) return 1;
+    const cplx v = hdot(ha.data(), hb.data(), n);
+    out_host[0] = v.real(), out_host[1] = v.imag();
     return 0;
 }
 
@@ -461,6 +531,25 @@ __attribute__((weak)) int htn_krylov_expm_z(const htn_gemm_launch* stages, int32
     int nmv = 0;
     const int rc = be->krylov_expm(stages, n_stages, x_slot, y_slot, V, n, krylovdim, dt_re, dt_im, tol, max_restart, zero_y, exchange, user,
                                    growth_host, alpha0_host, &nmv, err_host, matvec_ms_host);
+    *n_matvec_host = nmv;
+    return rc;
+}
+
+// Host-memory statement of the kernel-level entry (V, X and the buffers of the stages are host pointers; V holds krylovdim + 2
+// rows).  Weak: in libhubbardtn_hip.so the definition of htn_krylov.hip takes its place at link time.
+__attribute__((weak)) int htn_krylov_solve_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot, void* V, int64_t n,
+                                             int32_t krylovdim, double z_re, double z_im, double tol, int32_t max_restart, void* X,
+                                             int32_t use_guess, void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
+                                             double* norm_host, double* residual_host, int32_t* n_matvec_host, double* matvec_ms_host,
+                                             void* stream) {
+    (void)scratch, (void)stream;
+    if (!stages || !V || !X || !norm_host || !residual_host || !n_matvec_host) return set_error("htn_krylov_solve_z: bad arguments");
+    if (!(z_re - z_re == 0.0) || !(z_im - z_im == 0.0) || !(tol >= 0.0)) return set_error("htn_krylov_solve_z: z must be finite, tol >= 0");
+    std::unique_ptr<Backend> be(make_backend(HTN_BACKEND_CPU, 0, nullptr));
+    if (!be) return 1;
+    int nmv = 0;
+    const int rc = be->krylov_solve(stages, n_stages, x_slot, y_slot, V, n, krylovdim, z_re, z_im, tol, max_restart, X, use_guess, zero_y,
+                                    exchange, user, norm_host, residual_host, &nmv, matvec_ms_host);
     *n_matvec_host = nmv;
     return rc;
 }

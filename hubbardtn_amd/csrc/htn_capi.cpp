@@ -1,7 +1,7 @@
 // The C entry points of the bond-update / sweep level and of the IDMRG2 driver, grouped and ordered as the sections of
 // include/hubbardtn_hip.h.  Argument checks and forwarding; what an entry does lives with the htn_mps members it calls
 // (htn_engine.cpp, htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_idmrg.cpp).  The kernel-level entries that the CPU baseline library
-// exports too (htn_krylov_expm_z, htn_qr_blocks_z, htn_block_nullproj_z) are in htn_backend_host.cpp.  Host C++ (no HIP).
+// exports too (htn_krylov_expm_z, htn_krylov_solve_z, htn_qr_blocks_z, htn_block_nullproj_z) are in htn_backend_host.cpp.  Host C++ (no HIP).
 // NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
 #include "htn_engine.h"
 
@@ -210,6 +210,31 @@ int htn_heff0_apply(htn_mps* mps, int32_t b, const void* x_host, void* y_host) {
     auto ap = mps->make_apply0(b);
     if (!ap) return 1;
     return mps->apply_once(*ap, mps->Lbuf[b], mps->Rbuf[b], htn_mps_bond_size(mps, b), x_host, y_host, false);
+}
+// ---- correction-vector sweeps ---------------------------------------------------------------------------------------
+int htn_bond_solve(htn_mps* x, int32_t i, int32_t direction, int32_t placement, double z_re, double z_im, const htn_sweep_opts* opts,
+                   htn_bond_stats* stats, double* amp_host, double* bx_host) {
+    if (!x) return set_error("htn_bond_solve: bad arguments");
+    if (x->be->activate()) return 1;
+    const htn_sweep_opts o = norm_opts(opts);
+    if (x->cv_checks(o, "htn_bond_solve")) return 1;
+    if (!(z_re - z_re == 0.0) || !(z_im - z_im == 0.0)) return set_error("htn_bond_solve: z is not finite");
+    const cplx z(z_re, z_im);
+    double out[3] = {0.0, 0.0, 0.0};
+    if (x->update_bond(i, direction, placement == 0, false, o, stats, nullptr, nullptr, &z, out)) return 1;
+    if (amp_host) *amp_host = out[0];
+    if (bx_host) bx_host[0] = out[1], bx_host[1] = out[2];
+    return 0;
+}
+int htn_cv_sweep(htn_mps* x, double z_re, double z_im, const htn_sweep_opts* opts, htn_bond_stats* stats, double* amp_host, double* bx_host) {
+    if (!x) return set_error("htn_cv_sweep: bad arguments");
+    if (x->be->activate()) return 1;
+    if (!(z_re - z_re == 0.0) || !(z_im - z_im == 0.0)) return set_error("htn_cv_sweep: z is not finite");
+    double out[3] = {0.0, 0.0, 0.0};
+    if (x->cv_sweep(cplx(z_re, z_im), norm_opts(opts), stats, out)) return 1;
+    if (amp_host) *amp_host = out[0];
+    if (bx_host) bx_host[0] = out[1], bx_host[1] = out[2];
+    return 0;
 }
 int htn_mps_set_mpo(htn_mps* mps, const htn_mpo* mpo) {
     if (!mps || !mpo) return set_error("htn_mps_set_mpo: bad arguments");

@@ -347,6 +347,16 @@ struct Backend {
     virtual int krylov_expm(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim,
                             double dt_re, double dt_im, double tol, int max_restart, int zero_y, htn_exchange2_fn exchange, void* user,
                             double* growth, double* alpha0, int* n_matvec, double* err, double* matvec_ms);
+    // (z - H) x = b for b = the device row V[0], by the restarted minimal residual on the Lanczos basis (htn_krylov_solve_z in the
+    // header: outputs, stopping and restart rule); X: device buffer of n elements, the start value with use_guess, the solution on
+    // exit; V[0] = x / |x|, *norm = |x|.  NOT pure: the default (htn_backend_host.cpp) is a plain host statement of the method --
+    // vectors downloaded, H applied through grouped_gemm, full two-pass reorthogonalisation, the decisions of
+    // htn_resolvent::Resolvent -- which the CPU baseline library inherits; the HIP backend overrides it with htn_krylov_solve_z.
+    virtual int krylov_solve(const htn_gemm_launch* stages, int n_stages, int x_slot, int y_slot, void* V, int64_t n, int krylovdim,
+                             double z_re, double z_im, double tol, int max_restart, void* X, int use_guess, int zero_y,
+                             htn_exchange2_fn exchange, void* user, double* norm, double* residual, int* n_matvec, double* matvec_ms);
+    // out_host[0..1] = <a|b> = sum conj(a_e) b_e of two device vectors.  Default: on the host.
+    virtual int dotc(const void* a, const void* b, int64_t n, double* out_host);
     // Gram-Schmidt (two passes) of the nvec device rows P in place, in order; a row whose remainder falls below drop_tol x its
     // norm is dropped and the rows behind it move up.  -> *kept orthonormal rows.  Default: on the host.
     virtual int orthonormalise_rows(void* P, int64_t n, int nvec, double drop_tol, int* kept);

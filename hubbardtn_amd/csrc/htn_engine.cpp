@@ -165,7 +165,7 @@ void htn_mps::fill_stats(htn_bond_stats* st, int bond, int direction, const Solv
 
 // ---- two-site update, step by step ----------------------------------------------------------------
 // solve: theta -> V[0], the compiled apply, the projector rows of attached states (optimising updates), Lanczos
-int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w, const cplx* evolve_dt) {
+int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w, const cplx* evolve_dt, const cplx* solve_z) {
     w.tl = theta_layout(bonds[i], bonds[i + 2]);
     const ThetaLayout& tl = *w.tl;
     Solve& s = w.sol;
@@ -174,7 +174,29 @@ int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageCloc
     if (n <= 0) return set_error("htn_bond_update: empty two-site tensor on bond %d", i);
     w.V = zalloc((int64_t)(kd + 2) * n, false);
     if (!w.V.base) return set_error("device allocation of the Krylov basis failed (%lld elements)", (long long)((kd + 2) * n));
-    if (theta_into(i, tl, w.V.ptr())) return 1;                // theta -> V[0] (the Lanczos driver normalises it)
+    if (solve_z) {
+        // correction-vector update: V[0] = p = amplitude(b) x O_L theta_b O_R, the projected right-hand side (kept in Qb for
+        // <p|theta_new>); the start value is the state as it is, amplitude x theta
+        const OrthState& os = orth[0];
+        w.Qb = zalloc(n, false), w.X = zalloc(n, false);
+        if (!w.Qb.base || !w.X.base) return set_error("device allocation failed (right-hand side of the solve)");
+        if (ovl_project(os, i, tl, w.Qb.ptr())) return 1;
+        if (os.phi->amp != 1.0 && be->scale(w.Qb.ptr(), n, os.phi->amp)) return 1;
+        auto cp = cached<RelayC>(std::string("cvcopy") + std::string((const char*)&n, sizeof(n)), [&]() -> std::shared_ptr<RelayC> {
+            auto r = std::make_shared<RelayC>();
+            std::vector<htn_copy_item> items;
+            for (int64_t off = 0; off < n; off += 1 << 30) {
+                const int32_t rows = (int32_t)std::min<int64_t>(n - off, 1 << 30);
+                items.push_back(copy_item(off, rows, off, rows, rows, 1));
+            }
+            r->n = (int)items.size();
+            if (!(r->items = upload_vec(be, items))) return nullptr;
+            return r;
+        });
+        if (!cp || be->batched_copy(w.V.ptr(), w.Qb.ptr(), nullptr, nullptr, (const htn_copy_item*)cp->items->p, cp->n, 1.0)) return 1;
+        if (theta_into(i, tl, w.X.ptr())) return 1;
+        if (amp != 1.0 && be->scale(w.X.ptr(), n, amp)) return 1;
+    } else if (theta_into(i, tl, w.V.ptr())) return 1;         // theta -> V[0] (the Lanczos driver normalises it)
     s.ap = make_apply(i, tl);
     if (!s.ap) return 1;
     w.z = zalloc(s.ap->zsize, false);
@@ -197,7 +219,15 @@ int htn_mps::bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageCloc
         if (be->orthonormalise_rows(w.Qb.ptr(), n, na, 1e-12, &n_frozen)) return 1;
         orth_dropped = na - n_frozen;
     }
-    if (evolve_dt) {            // (evolving update: theta <- exp(-i dt H_eff) theta; E = <theta|H_eff|theta> before the step)
+    if (solve_z) {              // (theta <- (z - H_eff)^-1 p; E = Im <p|theta_new>, the spectral weight)
+        double bx[2];
+        if (be->krylov_solve(stages, ns, BUF_X, BUF_Y, w.V.ptr(), n, kd, solve_z->real(), solve_z->imag(), o.lanczos_tol, o.maxrestart,
+                             w.X.ptr(), 1, 0, nullptr, ctx, &s.xnorm, &s.res, &s.nmv, be->timing ? &s.mv_ms : nullptr))
+            return 1;
+        if (be->dotc(w.Qb.ptr(), w.X.ptr(), n, bx)) return 1;
+        s.bx = cplx(bx[0], bx[1]);
+        s.E = bx[1];
+    } else if (evolve_dt) {     // (evolving update: theta <- exp(-i dt H_eff) theta; E = <theta|H_eff|theta> before the step)
         if (be->krylov_expm(stages, ns, BUF_X, BUF_Y, w.V.ptr(), n, kd, evolve_dt->real(), evolve_dt->imag(), o.lanczos_tol, o.maxrestart, 0,
                             nullptr, ctx, &s.growth, &s.E, &s.nmv, &s.res, be->timing ? &s.mv_ms : nullptr))
             return 1;
@@ -450,11 +480,11 @@ void htn_mps::bond_spectrum(int i, const BondWork& w) {
 }
 
 int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st,
-                         const cplx* evolve_dt, double* log_growth) {
+                         const cplx* evolve_dt, double* log_growth, const cplx* solve_z, double* cv_out) {
     if (i < 0 || i + 1 >= L) return set_error("htn_bond_update: bond index %d out of range", i);
     StageClock clk(be, o.profile);
     BondWork w;
-    if (bond_solve(i, optimise, o, clk, w, evolve_dt)) return 1;          // (laps clk.plan and clk.lanczos)
+    if (bond_solve(i, optimise, o, clk, w, evolve_dt, solve_z)) return 1;          // (laps clk.plan and clk.lanczos)
     if (log_growth) *log_growth += log(w.sol.growth);
     const double t_svd0 = clk.last;
     if (bond_svd(i, right, o, w)) return 1;
@@ -467,9 +497,13 @@ int htn_mps::update_bond(int i, int direction, bool right, bool optimise, const 
     clk.svd = clk.lap();
     if (bond_advance(i, right)) return 1;
     clk.env = clk.lap();
-    energy = w.sol.E;
+    if (!solve_z) energy = w.sol.E;
     centre = right ? i + 1 : i;
     norm_absorbed();
+    if (solve_z) {              // the tensors are normalised; the norm of the solution is the state's amplitude
+        amp = w.sol.xnorm;
+        if (cv_out) cv_out[0] = amp, cv_out[1] = w.sol.bx.real(), cv_out[2] = w.sol.bx.imag();
+    }
     bond_spectrum(i, w);
     if (st) fill_stats(st, i + 1, direction, w.sol, Llay[i]->size + Rlay[i + 2]->size, w.jac_sweeps, w.sc->sp.flops, w.tw, clk);
     return 0;

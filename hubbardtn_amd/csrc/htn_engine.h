@@ -165,12 +165,15 @@ struct Solve {                     // the eigenproblem of one update (compiled a
     double E = 0.0, res = 0.0, mv_ms = 0.0;
     int nmv = 0;
     double growth = 1.0;           // evolving updates: |x| / |x0| of the exponential
+    double xnorm = 0.0;            // correction-vector updates: |theta_new| and <p|theta_new>
+    cplx bx = 0.0;
 };
 struct BondWork {                  // what flows between the steps of one two-site update (htn_mps::update_bond)
     ThetaLayoutP tl;
     Solve sol;
     // device buffers: all live until the update returns and go back to the pool in reverse order of declaration
     DView V, z, Qb;                // Krylov basis (row 0: theta, then the optimised tensor); Z stage of the apply; projector rows
+    DView X;                       // correction-vector updates: start value, then the solution (Qb: the right-hand side)
     std::shared_ptr<SvdC> sc;
     DView G, Vj;
     DBufP S, idx;                  // s_elems singular values | per-block sweep counts (int32); kept columns, block after block
@@ -213,7 +216,8 @@ struct htn_mps {
     int centre = 0;                     // site that carries the centre (htn_mps_create: 0; every update moves it)
     // Every update normalises the tensors it writes.  A state made by htn_mps_apply_op carries <O psi|O psi> in its tensors
     // (raw_n2 >= 0) until its first update, and from then on beside them: the state is amp x (the stored tensors).  Overlaps and
-    // transition amplitudes multiply by amp; every other state has amp = 1 and raw_n2 < 0 for life.
+    // transition amplitudes multiply by amp; every other state has amp = 1 and raw_n2 < 0 for life -- but a correction vector
+    // (htn_bond_solve / htn_cv_sweep), whose amp is the norm of its last local solution.
     double amp = 1.0, raw_n2 = -1.0;
     void norm_absorbed() {
         if (raw_n2 >= 0.0) amp = sqrt(raw_n2), raw_n2 = -1.0;
@@ -320,7 +324,8 @@ struct htn_mps {
     int apply_once(const ApplyC& ap, const DView& L, const DView& R, int64_t n, const void* x_host, void* y_host, bool exchange);
     int theta_into(int i, const ThetaLayout& tl, cplx* dst);
     // two-site update: update_bond runs these once each, in this order
-    int bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w, const cplx* evolve_dt = nullptr);
+    int bond_solve(int i, bool optimise, const htn_sweep_opts& o, StageClock& clk, BondWork& w, const cplx* evolve_dt = nullptr,
+                   const cplx* solve_z = nullptr);
     std::shared_ptr<SvdC> make_svd(int i, const ThetaLayout& tl, bool right);
     int bond_svd(int i, bool right, const htn_sweep_opts& o, BondWork& w);
     int bond_truncate(int i, const htn_sweep_opts& o, BondWork& w);
@@ -330,7 +335,10 @@ struct htn_mps {
     void fill_stats(htn_bond_stats* st, int bond, int direction, const Solve& sol, int64_t env_elems, int jacobi_sweeps,
                     int64_t svd_flops, double trunc_weight, const StageClock& clk);
     int update_bond(int i, int direction, bool right, bool optimise, const htn_sweep_opts& o, htn_bond_stats* st,
-                    const cplx* evolve_dt = nullptr, double* log_growth = nullptr);
+                    const cplx* evolve_dt = nullptr, double* log_growth = nullptr, const cplx* solve_z = nullptr, double* cv_out = nullptr);
+    // correction-vector sweeps (htn_bond_solve / htn_cv_sweep): update_bond with Backend::krylov_solve as the solver
+    int cv_checks(const htn_sweep_opts& o, const char* who) const;
+    int cv_sweep(cplx z, const htn_sweep_opts& o, htn_bond_stats* st, double* cv_out);
     int sweep(const htn_sweep_opts& o, htn_bond_stats* st, double* E);
     int set_mpo(htn_mpo* m);
     // ---- htn_site.cpp: one-site DMRG (htn_site_update / htn_dmrg1_sweep) and time evolution (htn_bond_evolve /

@@ -17,6 +17,7 @@
 
 #include "htn_common.h"
 #include "htn_expm.h"
+#include "htn_resolvent.h"
 #include "htn_tridiag.h"
 
 #define DOT_BLOCKS HTN_DOT_BLOCKS   // partial sums per vector = slices of the vector (4 per lane of the reducing wave)
@@ -503,6 +504,49 @@ static void launch_krylov_combine(double2* V, int64_t ldv, int nvec, int64_t n, 
 #undef HTN_KC
 }
 
+// Shifted solve (htn_krylov_solve_z): the two updates that end a restart cycle in ONE launch,
+//   X <- (keep ? X : 0) + sum_{i < m} y_i V[i]        and, with have_rho,        V[0] <- sum_{i <= m} rho_i V[i].
+// Both coefficient sets travel BY VALUE (2 x 32 double2 = 1 KiB of kernel arguments: no staging buffer, nothing to drain); the
+// host pads them with zeros, so one row count (nvec = the rows read) serves both sums.  A thread reads its element of every row
+// and of X (CH + 1 16-byte loads in flight, coalesced down each row; rows past nvec are clamped re-reads with coefficient 0)
+// BEFORE it writes its element of X and of row 0, and no other thread touches that element: both in-place updates are safe.
+// Memory bound: (nvec + 1) n 16 B read, 2 n 16 B written; without rho (a converged cycle) only X is written.
+struct KrylovCoef2 {
+    double2 y[DOT_CHUNK], r[DOT_CHUNK];
+};
+template <int CH, int TH>
+__global__ __launch_bounds__(TH) void k_krylov_combine2(double2* V, int64_t ldv, int nvec, int64_t n, double2* __restrict__ X, int keep,
+                                                        int have_rho, const KrylovCoef2 kc) {
+    for (int64_t j = (int64_t)blockIdx.x * TH + threadIdx.x; j < n; j += (int64_t)gridDim.x * TH) {
+        double2 v[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int i = c < nvec ? c : nvec - 1;
+            v[c] = V[(int64_t)i * ldv + j];
+        }
+        double2 x = make_double2(0.0, 0.0);
+        if (keep) x = X[j];
+        double sr = 0.0, si = 0.0, tr = 0.0, ti = 0.0;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {                    // kc.y[c] = kc.r[c] = 0 beyond their counts
+            sr += kc.y[c].x * v[c].x - kc.y[c].y * v[c].y;
+            si += kc.y[c].x * v[c].y + kc.y[c].y * v[c].x;
+            tr += kc.r[c].x * v[c].x - kc.r[c].y * v[c].y;
+            ti += kc.r[c].x * v[c].y + kc.r[c].y * v[c].x;
+        }
+        X[j] = make_double2(x.x + sr, x.y + si);
+        if (have_rho) V[j] = make_double2(tr, ti);
+    }
+}
+
+static void launch_krylov_combine2(double2* V, int64_t ldv, int nvec, int64_t n, double2* X, int keep, int have_rho, const KrylovCoef2& kc,
+                                   hipStream_t st) {
+#define HTN_KC2(CHV, THV) \
+    hipLaunchKernelGGL((k_krylov_combine2<CHV, THV>), dim3(grid_for(n)), dim3(THV), 0, st, V, ldv, nvec, n, X, keep, have_rho, kc)
+    HTN_CH_DISPATCH(nvec, dot_slice(n), HTN_KC2);
+#undef HTN_KC2
+}
+
 extern "C" int64_t htn_dots_scratch_elems(int32_t nvec) { return (int64_t)nvec * DOT_BLOCKS; }
 
 extern "C" int htn_dots_z(const void* V, int64_t ldv, int32_t nvec, const void* w, int64_t n, void* out,
@@ -617,6 +661,14 @@ static bool lan_expect_convergence(const std::vector<double>& res, double tol) {
 // process totals for HTN_DEBUG_HOST_TIMERS: closed steps that converged / that did not; convergences at an open step
 static std::atomic<long long> g_lan_close_hit{0}, g_lan_close_miss{0}, g_lan_open_conv{0};
 
+// what lanczos_run needs of a shifted solve besides the host decisions: the caller's X and what became of it
+struct SolveHook {
+    htn_resolvent::Resolvent rs;
+    double2* X = nullptr;
+    bool use_guess = false;
+    double xnorm = 0.0;
+};
+
 // The driver of htn_lanczos_z (nf = 0) and htn_lanczos_orth_z (nf frozen rows Q: lowest eigenpair of P H P, P = 1 - Q Q^H).
 // With frozen rows every pass of a step runs over Q followed by the Krylov rows: the first (short) pass takes the dots with
 // Q AND {V[j-1], V[j]} -- H v_j has O(|H|) components along Q, not O(eps |H|) -- and the second pass is the full one it always
@@ -626,7 +678,8 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
                        void* Vv, int64_t n, int32_t krylovdim, double tol, int32_t max_restart,
                        void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user,
                        double* eig_host, int32_t* n_matvec_host, double* residual_host,
-                       double* matvec_ms_host, void* stream_v, const double2* Q, int nf, htn_expm::Expm* ex = nullptr) {
+                       double* matvec_ms_host, void* stream_v, const double2* Q, int nf, htn_expm::Expm* ex = nullptr,
+                       SolveHook* sv = nullptr) {
     hipStream_t st = (hipStream_t)stream_v;
     const int kd = krylovdim;
     const int kt = kd + nf;                                        // rows of the widest pass + 1
@@ -643,7 +696,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
     const bool event_waits = htn_debug_event_waits();
     static const bool full_first_pass = htn_env_flag("HTN_LANCZOS_FULL_FIRST_PASS");
 
-    const LanClose close_mode = ex ? LAN_CLOSE_NEVER : lan_close_mode();
+    const LanClose close_mode = ex || sv ? LAN_CLOSE_NEVER : lan_close_mode();
     bool timed_step[LAN_SLOTS] = {false};
     bool closed[LAN_SLOTS] = {false};             // the step published its own record (k_publish_record)
     unsigned long long step_serial[LAN_SLOTS] = {0};
@@ -755,14 +808,66 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
             launch_axpy_norm(w, Q, n, nf, partial, c1, -1, -1.0, n, norm_partial, st);
         }
     };
+    double mv_ms = 0.0;
+    int nmv = 0, n_timed = 0;
+    // (shifted solve) the squared norm in norm_partial -> host: the record of the last slot, which no step uses (krylovdim <= 31)
+    auto fetch_norm2 = [&](double* out) -> int {
+        const int q = LAN_SLOTS - 1;
+        step_serial[q] = ++R->serial;
+        hipLaunchKernelGGL(k_publish_record, dim3(1), dim3(64), 0, st, (const double*)norm_partial, (const double2*)c1, (const double2*)c2,
+                           R->d_rec + q, step_serial[q]);
+        if (event_waits) HIP_TRY(hipEventRecord(R->ev_done[q], st));
+        double a1 = 0.0, a2 = 0.0;
+        if (wait_step(q, &a1, &a2, out)) return 1;
+        if (!(*out == *out)) return fail_msg("htn_krylov_solve_z: NaN in a vector norm (operator, right-hand side or start value not finite)");
+        return 0;
+    };
+    // (shifted solve) |X| -> host, V[0] = X / |X|: the end of every solve whose norm the host does not know already
+    auto normalise_x = [&]() -> int {
+        double x2 = 0.0;
+        hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, (const double2*)sv->X, n, norm_partial);
+        if (fetch_norm2(&x2)) return 1;
+        hipLaunchKernelGGL(k_scale_by_norm, dim3(grid_for(n)), dim3(DOT_THREADS), 0, st, V, (const double2*)sv->X, norm_partial, n,
+                           (LanRecord*)nullptr, (const double2*)nullptr, (const double2*)nullptr, 0ull);
+        sv->xnorm = sqrt(x2);
+        return 0;
+    };
     // normalise the start vector (frozen rows: projected first)
     if (nf > 0) project_out(V);
     else
     hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, n, norm_partial);
+    if (sv) {
+        // |b| is the scale of the stopping rule; with a start value the basis is built from r0 = b - z x0 + H x0 (one matvec into
+        // row 1, two axpys with the coefficients in the unused y block of the scratch)
+        double b2 = 0.0, r2 = 0.0;
+        if (fetch_norm2(&b2)) return 1;
+        if (!(b2 > 0.0)) return fail_msg("htn_krylov_solve_z: the right-hand side is zero");
+        sv->rs.bnorm = sqrt(b2);
+        r2 = b2;
+        if (sv->use_guess) {
+            const double2 h[2] = {make_double2(-sv->rs.z.real(), -sv->rs.z.imag()), make_double2(1.0, 0.0)};
+            HIP_TRY(hipMemcpyAsync(ycoef, h, sizeof(h), hipMemcpyHostToDevice, st));
+            HIP_TRY(htn_stream_spin(st));                    // (h is on this frame)
+            if (matvec(sv->X, V + n, nullptr)) return 1;
+            ++nmv;
+            hipLaunchKernelGGL(k_axpys, dim3(grid_for(n)), dim3(256), 0, st, V, (const double2*)sv->X, n, 1, (const double2*)ycoef, 1.0, n);
+            hipLaunchKernelGGL(k_axpys, dim3(grid_for(n)), dim3(256), 0, st, V, (const double2*)(V + n), n, 1, (const double2*)(ycoef + 1), 1.0, n);
+            hipLaunchKernelGGL(k_norm_partial, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, V, n, norm_partial);
+            if (fetch_norm2(&r2)) return 1;
+        }
+        sv->rs.begin_cycle(sqrt(r2 > 0.0 ? r2 : 0.0));
+        if (sv->rs.converged) {                              // the start value solves the system: x = x0
+            if (!sv->use_guess) return fail_msg("htn_krylov_solve_z: tol >= 1 accepts x = 0");
+            if (normalise_x()) return 1;
+            HIP_TRY(hipGetLastError());
+            *n_matvec_host = nmv;
+            *residual_host = sv->rs.resid;
+            if (matvec_ms_host) *matvec_ms_host = -1.0;
+            return 0;
+        }
+    }
     hipLaunchKernelGGL(k_scale_by_norm, dim3(grid_for(n)), dim3(DOT_THREADS), 0, st, V, V, norm_partial, n,
                        (LanRecord*)nullptr, (const double2*)nullptr, (const double2*)nullptr, 0ull);
-    double mv_ms = 0.0;
-    int nmv = 0, n_timed = 0;
     static const bool dbg_timers = getenv("HTN_DEBUG_HOST_TIMERS") != nullptr;
     auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_enq = 0.0, t_wait = 0.0, t_host = 0.0;
@@ -818,6 +923,12 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
                 if (stop) break;
                 continue;
             }
+            if (sv) {
+                const bool stop = sv->rs.step(alpha, beta, kd);
+                t_host += now_us() - tq;
+                if (stop) break;
+                continue;
+            }
             alphas.push_back(alpha);
             tridiag_lowest(alphas, betas, &theta, y);
             res = fabs(beta * y.back());
@@ -855,6 +966,52 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
             if (ex->remaining == 0.0) break;
             continue;
         }
+        if (sv) {
+            // The end of this cycle in one launch (k_krylov_combine2), ordered on the stream behind the speculative step like the
+            // combination of the exponential: that step wrote row m + 1, this reads rows 0 .. m.  The rows 0 .. m - 1 are unit
+            // vectors; row m, read only when the cycle ran to krylovdim without converging, is the RAW vector its (closed) step left
+            // behind, beta_m v_m: its coefficient carries 1 / beta_m.  The next start vector has norm |rho| by construction, so
+            // the coefficients are handed over divided by it and the host knows beta_0 of the next cycle without a norm pass.
+            htn_resolvent::Resolvent& rs = sv->rs;
+            if (!rs.converged && restart == max_restart) {
+                HIP_TRY(htn_stream_spin(st));
+                snprintf(htn_err_buf(), 512, "htn_krylov_solve_z: not converged after %d restart(s) of krylovdim %d: relative residual %.3e remains "
+                         "(tol %.3e)", max_restart, kd, rs.resid, rs.tol);
+                return 1;
+            }
+            const double ynorm = rs.finish();
+            const int m = (int)rs.y.size();
+            const bool keep = sv->use_guess || restart > 0;
+            KrylovCoef2 kc;
+            for (int i = 0; i < DOT_CHUNK; ++i) {
+                kc.y[i] = i < m ? make_double2(rs.y[i].real(), rs.y[i].imag()) : make_double2(0.0, 0.0);
+                kc.r[i] = make_double2(0.0, 0.0);
+            }
+            if (rs.converged && !keep && ynorm > 0.0) {      // one cycle from zero: |x| = |y|_2, and row 0 becomes x / |x| on the way
+                for (int i = 0; i < m; ++i) kc.r[i] = make_double2(rs.y[i].real() / ynorm, rs.y[i].imag() / ynorm);
+                launch_krylov_combine2(V, n, m, n, sv->X, 0, 1, kc, st);
+                sv->xnorm = ynorm;
+                break;
+            }
+            if (rs.converged) {
+                launch_krylov_combine2(V, n, m, n, sv->X, keep ? 1 : 0, 0, kc, st);
+                if (normalise_x()) return 1;
+                break;
+            }
+            const double rn = rs.rho_norm();
+            if (!(rn > 0.0) || !(beta > 0.0)) return fail_msg("htn_krylov_solve_z: the residual of an unconverged cycle vanished");
+            for (int i = 0; i <= m; ++i) {
+                const double f = i == m ? 1.0 / (rn * beta) : 1.0 / rn;
+                kc.r[i] = make_double2(rs.rho[i].real() * f, rs.rho[i].imag() * f);
+            }
+            launch_krylov_combine2(V, n, m + 1, n, sv->X, keep ? 1 : 0, 1, kc, st);
+            rs.begin_cycle(rn);
+            if (rs.converged) {                                  // (|rho| against the rotated residual: a tie at the tolerance)
+                if (normalise_x()) return 1;
+                break;
+            }
+            continue;
+        }
         // x = sum_i y_i V_i in place in row 0, then normalised: the combine launch of the exponential with the real Ritz
         // coefficients BY VALUE -- no staging buffer, no copy, no memset, and so nothing of the host's to protect by a drain.
         // Per element it is the sum the driver used to take (from zero, i = 0 .. k - 1 in order, the imaginary part of every
@@ -887,7 +1044,7 @@ static int lanczos_run(const htn_gemm_launch* stages, int32_t n_stages, int32_t 
                 now_us() - t_begin, t_enq, t_wait, t_host, g_lan_close_hit.load(), g_lan_close_miss.load(), g_lan_open_conv.load());
     *eig_host = ex ? ex->alpha0 : theta;
     *n_matvec_host = nmv;
-    *residual_host = ex ? ex->err_total : res;
+    *residual_host = ex ? ex->err_total : sv ? sv->rs.resid : res;
     // sampled launches scaled to all launches of this solve (the next solves continue the 1-in-8 sampling phase)
     if (matvec_ms_host) *matvec_ms_host = n_timed ? mv_ms * nmv / n_timed : -1.0;
     return 0;
@@ -946,5 +1103,41 @@ extern "C" int htn_krylov_expm_z(const htn_gemm_launch* stages, int32_t n_stages
     *growth_host = ex.growth;
     *alpha0_host = a0;
     *err_host = err;
+    return 0;
+}
+
+// X <- (keep ? X : 0) + sum_{i < m} y[i] V[i] and, with rho, V[0] <- sum_{i <= m} rho[i] V[i] (hubbardtn_hip.h): the launch on its own
+extern "C" int htn_krylov_combine2_z(void* V, int64_t ldv, int32_t m, const double* y_host, const double* rho_host, void* X, int32_t keep,
+                                     int64_t n, void* stream) {
+    if (m < 1 || m + 1 > DOT_CHUNK) return fail_msg("htn_krylov_combine2_z: m must be in 1..31");
+    if (!V || !X || !y_host || n < 0 || ldv < n) return fail_msg("htn_krylov_combine2_z: bad arguments (V, X, y_host, 0 <= n <= ldv)");
+    if (n == 0) return 0;
+    KrylovCoef2 kc;
+    for (int i = 0; i < DOT_CHUNK; ++i) {
+        kc.y[i] = i < m ? make_double2(y_host[2 * i], y_host[2 * i + 1]) : make_double2(0.0, 0.0);
+        kc.r[i] = rho_host && i <= m ? make_double2(rho_host[2 * i], rho_host[2 * i + 1]) : make_double2(0.0, 0.0);
+    }
+    launch_krylov_combine2((double2*)V, ldv, rho_host ? m + 1 : m, n, (double2*)X, keep ? 1 : 0, rho_host ? 1 : 0, kc, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// (z - H) x = b by the restarted minimal residual on the basis lanczos_run builds (hubbardtn_hip.h; the host decisions are
+// htn_resolvent::Resolvent's)
+extern "C" int htn_krylov_solve_z(const htn_gemm_launch* stages, int32_t n_stages, int32_t x_slot, int32_t y_slot, void* Vv, int64_t n,
+                                  int32_t krylovdim, double z_re, double z_im, double tol, int32_t max_restart, void* X, int32_t use_guess,
+                                  void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user, double* norm_host,
+                                  double* residual_host, int32_t* n_matvec_host, double* matvec_ms_host, void* stream_v) {
+    if (krylovdim < 2 || krylovdim + 1 > DOT_CHUNK) return fail_msg("htn_krylov_solve_z: krylovdim must be in 2..31");
+    if (!Vv || !X || !scratch || n <= 0 || !norm_host || !residual_host || !n_matvec_host) return fail_msg("htn_krylov_solve_z: bad arguments");
+    if (!(z_re - z_re == 0.0) || !(z_im - z_im == 0.0) || !(tol >= 0.0)) return fail_msg("htn_krylov_solve_z: z must be finite, tol >= 0");
+    SolveHook sv;
+    sv.rs.z = htn_resolvent::cplx(z_re, z_im), sv.rs.tol = tol;
+    sv.X = (double2*)X, sv.use_guess = use_guess != 0;
+    double unused = 0.0;
+    if (lanczos_run(stages, n_stages, x_slot, y_slot, Vv, n, krylovdim, tol, max_restart < 0 ? 0 : max_restart, scratch, zero_y, exchange,
+                    user, &unused, n_matvec_host, residual_host, matvec_ms_host, stream_v, nullptr, 0, nullptr, &sv))
+        return 1;
+    *norm_host = sv.xnorm;
     return 0;
 }

@@ -314,3 +314,33 @@ int htn_mps::tdvp1_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, d
     if (log_norm) *log_norm = lg;
     return 0;
 }
+
+// =====================================================================================================================
+// Correction-vector sweeps (htn_bond_solve / htn_cv_sweep).  A bond step is update_bond with
+// Backend::krylov_solve in the place of the eigen-solve: (z - H_eff) theta = p, p the row the attached-state machinery forms for
+// the ONE attached state b (times its amplitude, before any orthonormalisation), started from the state as it is.  The tensors
+// stay normalised; the norm of the last solution is the state's amplitude.
+// =====================================================================================================================
+int htn_mps::cv_checks(const htn_sweep_opts& o, const char* who) const {
+    if (ctx->world > 1 || ctx->shard || ctx->exch || be->has_comm())
+        return set_error("%s: a correction-vector solve on a context with a communicator or an exchange hook is not supported", who);
+    if (orth.size() != 1)
+        return set_error("%s: the state has %d attached state(s): exactly one is read as the right-hand side (htn_mps_set_orthogonal)", who,
+                         (int)orth.size());
+    if (Llay[0]->size != 0 || Rlay[L]->size != 0)
+        return set_error("%s: a chain with boundary environments (an iDMRG window) is not supported", who);
+    if (o.krylovdim < 2 || o.krylovdim > 31) return set_error("%s: krylovdim = %d (must be in 2..31)", who, o.krylovdim);
+    return 0;
+}
+
+int htn_mps::cv_sweep(cplx z, const htn_sweep_opts& o, htn_bond_stats* st, double* cv_out) {
+    if (cv_checks(o, "htn_cv_sweep")) return 1;
+    if (L < 2) return set_error("htn_cv_sweep: a chain of %d site(s) has no bond to sweep over", L);
+    if (centre != 0) return set_error("htn_cv_sweep: the centre is on site %d, not on site 0", centre);
+    int k = 0;
+    for (int i = 0; i < L - 1; ++i, ++k)
+        if (update_bond(i, +1, true, false, o, st ? st + k : nullptr, nullptr, nullptr, &z, cv_out)) return 1;
+    for (int i = L - 2; i >= 0; --i, ++k)
+        if (update_bond(i, -1, false, false, o, st ? st + k : nullptr, nullptr, nullptr, &z, cv_out)) return 1;
+    return 0;
+}

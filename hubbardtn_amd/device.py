@@ -300,6 +300,39 @@ class HipOps:
         abi.check(self.lib, rc, "htn_krylov_expm_z")
         return growth.value, a0.value, nmv.value, err.value
 
+    def krylov_combine2(self, V, ldv, m, y, rho, X, keep, n):
+        """htn_krylov_combine2_z: X[0:n] <- (keep ? X : 0) + sum_{i < m} y[i] V[i] and, with rho (m + 1 entries, or None),
+        V[0:n] <- sum_{i <= m} rho[i] V[i] in place, one launch; y, rho: host complex arrays (passed to the kernel by value)"""
+        yh = np.ascontiguousarray(y, dtype=np.complex128)
+        rh = None if rho is None else np.ascontiguousarray(rho, dtype=np.complex128)
+        assert yh.shape == (m,) and (rh is None or rh.shape == (m + 1,))
+        abi.check(self.lib, self.lib.htn_krylov_combine2_z(self._p(V), int(ldv), int(m), yh.ctypes.data,
+                                                           None if rh is None else rh.ctypes.data, self._p(X), 1 if keep else 0,
+                                                           int(n), self._stream()), "htn_krylov_combine2_z")
+
+    def krylov_solve(self, stages, x_slot, y_slot, V, n, krylovdim, z, tol, max_restart, X, use_guess=False, zero_y=False):
+        """htn_krylov_solve_z: (z - H) x = b for the Hermitian map defined by `stages` (as for lanczos), b = V[0:n]; X: device
+        tensor of n elements, the start value with use_guess, x on return; V[0:n] <- x / |x|.  Returns (|x|, relative residual
+        of the recurrence, n_matvec)."""
+        arr = (abi.GemmLaunch * len(stages))()
+        keep = []
+        for k, (bufs, (tiles, ntiles, segs)) in enumerate(stages):
+            for b in range(abi.HTN_MAX_BUFS):
+                arr[k].bufs[b] = 0 if bufs[b] is None else bufs[b].data_ptr()
+            arr[k].tiles, arr[k].segs, arr[k].n_tiles = tiles.data_ptr(), segs.data_ptr(), ntiles
+            keep.append((bufs, tiles, segs))
+        need = self.lib.htn_lanczos_scratch_elems(max(int(krylovdim), 2))
+        if getattr(self, "_lan_scratch", None) is None or self._lan_scratch.numel() < need:
+            self._lan_scratch = self.empty_z(need)
+        z = complex(z)
+        nrm, res, nmv = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+        rc = self.lib.htn_krylov_solve_z(arr, len(stages), x_slot, y_slot, self._p(V), n, int(krylovdim), z.real, z.imag, float(tol),
+                                         int(max_restart), self._p(X), 1 if use_guess else 0, self._p(self._lan_scratch),
+                                         1 if zero_y else 0, abi.EXCHANGE_FN(), None, C.byref(nrm), C.byref(res), C.byref(nmv), None,
+                                         self._stream())
+        abi.check(self.lib, rc, "htn_krylov_solve_z")
+        return nrm.value, res.value, nmv.value
+
     def jacobi_svd(self, G, Vj, S, desc_dev, nblocks, max_m, max_sweeps, tol, info, desc_host=None, split=0, rank_cut=0.0,
                    sweeps_hint=0):
         """split: elements of R^H above which a block takes the large-block SVD path (0 = default);

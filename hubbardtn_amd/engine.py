@@ -540,6 +540,47 @@ class DMRG2:
         self.log_norm = lg.value
         return self.energy
 
+    # ---- correction-vector sweeps (htn_bond_solve / htn_cv_sweep) ------------------------------------------------
+    @property
+    def amplitude(self) -> float:
+        """the factor beside the (normalised) stored tensors: 1 for every state but the result of apply_op (the applied norm)
+        and a correction vector (|theta_new| of its last solve); `overlap` and `transition` apply it inside the library"""
+        a = self.__dict__.get("_amplitude")
+        if a is None:
+            n2 = self.__dict__.get("applied_norm2")
+            a = 1.0 if n2 is None else float(np.sqrt(max(n2, 0.0)))
+        return a
+
+    def solve_bond(self, i, direction, placement, z, record=True):
+        """theta <- (z - H_eff)^-1 p on sites (i, i+1), p the projection of the ONE attached state (set_orthogonal([b])) times its
+        amplitude, started from the current theta; then SVD, truncation, write-back and environment move as update_bond.
+        lanczos_tol is the tolerance of the solve.  -> (BondStats with energy = Im <p|theta_new> and residual = the relative
+        residual of the solve, <p|theta_new> = <b|x> before truncation, amplitude)"""
+        self.__dict__.pop("_bond_cache", None)
+        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
+        o, z = self._opts(), complex(z)
+        amp, bx = C.c_double(0.0), (C.c_double * 2)()
+        self._check(self.lib.htn_bond_solve(self.handle, i, direction, 0 if placement == "right" else 1, z.real, z.imag, C.byref(o),
+                                            st.ctypes.data, C.byref(amp), bx), "htn_bond_solve")
+        s = _stats(st[0])
+        if record:
+            self.stats.append(s)
+        self._amplitude = amp.value
+        return s, complex(bx[0], bx[1]), amp.value
+
+    def cv_sweep(self, z):
+        """one correction-vector sweep for (z - H) x = b, one library call: bonds 0..L-2 rightwards, L-2..0 leftwards (2L-2
+        records); the centre starts and ends on site 0.  -> (<b|x> of the last bond before its truncation, amplitude): the state
+        is amplitude x (the normalised stored tensors)."""
+        self.__dict__.pop("_bond_cache", None)
+        st = np.zeros(2 * self.L - 2, dtype=abi.BOND_STATS_DT)
+        o, z = self._opts(), complex(z)
+        amp, bx = C.c_double(0.0), (C.c_double * 2)()
+        self._check(self.lib.htn_cv_sweep(self.handle, z.real, z.imag, C.byref(o), st.ctypes.data, C.byref(amp), bx), "htn_cv_sweep")
+        self.stats.extend(_stats(r) for r in st)
+        self._amplitude = amp.value
+        return complex(bx[0], bx[1]), amp.value
+
     def bond_size(self, b) -> int:
         """elements of a vector in bond layout on bond b: one n_c x n_c column-major matrix per sector, in the order of
         `bonds[b]` (the layout of the triangular factors of a gauge move)"""

@@ -179,6 +179,33 @@ int htn_krylov_expm_z(const htn_gemm_launch* stages_host, int32_t n_stages, int3
                       double* growth_host, double* alpha0_host, int32_t* n_matvec_host, double* err_host,
                       double* matvec_ms_host, void* stream);
 
+/* Shifted linear solve (z - H) x = b for the Hermitian map given as stages (as for htn_lanczos_z), z = z_re + i z_im any finite
+ * complex number (Im z < 0: the hole part of a Green's function), b = V[0:n], not normalised.  The correction-vector equation of
+ * one frequency.  Method: minimal residual on the Lanczos basis (K(z - H, r) = K(H, r)), built by the step kernels and the
+ * depth-1 pipeline of htn_lanczos_z.  After step m the host minimises | beta_0 e_1 - (z I~ - T~_{m+1,m}) y | by Givens rotations
+ * on the (m + 1) x m complex tridiagonal matrix; the residual norm comes out of the rotations, no matvec is spent on it.  Stop at
+ * |r| <= tol |b|, at beta_m < 1e-14 x (largest |alpha| or beta seen: an invariant subspace), or at m = krylovdim.  Not converged
+ * there: x <- x + V_m y and the basis is rebuilt from r = V_{m+1} rho, rho = beta_0 e_1 - (z I~ - T~) y -- both updates in ONE
+ * launch (htn_krylov_combine2_z); at most max_restart restarts, then the call fails and the error names the relative residual
+ * that remains.  The restarted form converges for Im z != 0 (the field of values of z - H lies on the line Im = Im z); for real
+ * z it may stagnate and then reports that.
+ * use_guess != 0: X holds a start value x0; r0 = b - z x0 + H x0 costs one matvec and the solve is for the correction.
+ * V, scratch, krylovdim (2..31), zero_y, exchange: as for htn_lanczos_z (V: at least krylovdim + 1 rows; the CPU baseline
+ * library wants krylovdim + 2).  X: a caller buffer of n elements.  On exit X = x, V[0:n] = x / |x|, *norm_host = |x|,
+ * *residual_host = the last relative residual |r| / |b| of the recurrence, *n_matvec_host = matvecs enqueued (the one of r0 and
+ * speculative ones included).  Only step records and norms (32 bytes each) are read back.  The CPU baseline library exports the
+ * symbol with host pointers and no kernels (full two-pass reorthogonalisation, the same decisions: htn_resolvent.h). */
+int htn_krylov_solve_z(const htn_gemm_launch* stages_host, int32_t n_stages, int32_t x_slot, int32_t y_slot, void* V, int64_t n,
+                       int32_t krylovdim, double z_re, double z_im, double tol, int32_t max_restart, void* X, int32_t use_guess,
+                       void* scratch, int32_t zero_y, htn_exchange2_fn exchange, void* user, double* norm_host,
+                       double* residual_host, int32_t* n_matvec_host, double* matvec_ms_host, void* stream);
+/* The launch that ends a cycle of htn_krylov_solve_z on its own: X[0:n] <- (keep ? X : 0) + sum_{i < m} y[i] V[i * ldv : i * ldv + n]
+ * and, with rho_host != NULL, V[0:n] <- sum_{i <= m} rho[i] V[i * ldv : ...] in place; m in 1..31, y_host = m and rho_host = m + 1
+ * complex128 (re, im pairs) in HOST memory, passed to the kernel by value.  Rows 1.. are only read; without rho_host row 0 is only
+ * read too.  HIP library only. */
+int htn_krylov_combine2_z(void* V, int64_t ldv, int32_t m, const double* y_host, const double* rho_host, void* X, int32_t keep,
+                          int64_t n, void* stream);
+
 /* Batched one-sided Jacobi SVD of the coupled-sector blocks of a two-site tensor.
  * Stands in for: TensorKit tsvd!(t; alg=SVD()) -> LAPACK zgesvd per block (SURVEY.md 8a a9,
  * scheme chosen at src/HubbardFunctions.jl:1010 and :1363-1365).
@@ -595,6 +622,28 @@ int htn_tdvp1_sweep(htn_mps* mps, double dt_re, double dt_im, const htn_sweep_op
                     double* energy_host, double* log_norm_host);
 int64_t htn_mps_bond_size(htn_mps* mps, int32_t b);
 int htn_heff0_apply(htn_mps* mps, int32_t b, const void* x_host, void* y_host);
+
+/* Frequency-space Green's functions: correction-vector sweeps.  For one z the state x is swept towards the solution of
+ * (z - H) |x> = |b>, b the ONE state attached by htn_mps_set_orthogonal(x, &b, 1) (read as the right-hand side, e.g. the result
+ * of htn_mps_apply_op); then <O_x' psi0|x> of all sites by htn_mps_transition.  z = E0 + omega + i eta gives the particle part;
+ * the hole part solves with z = E0 - omega - i eta (Im z < 0) and flips the overall sign.
+ * htn_bond_solve: htn_bond_update with the eigen-solve replaced by htn_krylov_solve_z for (z - H_eff2) theta = p, where
+ *   p = amplitude(b) x O_L theta_b O_R is the row the attached-state machinery forms, BEFORE orthonormalisation, and the start
+ *   value is the current theta times the state's amplitude.  theta formation, per-sector SVD, truncation by opts, write-back and
+ *   the move of the H and overlap environments are those of htn_bond_update.  The stored tensors stay normalised, as in TDVP2;
+ *   the norm |theta_new| of the last solve is the state's AMPLITUDE: the state is amplitude x (stored tensors), the factor
+ *   htn_mps_apply_op introduced, which htn_mps_overlap and htn_mps_transition apply.  *amp_host = that amplitude,
+ *   bx_host[0..1] = <p|theta_new> = <b|x> before truncation.  stats: residual = the relative residual of the solve,
+ *   energy = Im <p|theta_new> (the spectral weight, the quantity DDMRG converges), the rest as for a bond update.  opts:
+ *   krylovdim (2..31), lanczos_tol (the tolerance of the solve), maxrestart, truncation and SVD settings.
+ * htn_cv_sweep: bonds 0 .. L-2 rightwards (placement right), then L-2 .. 0 leftwards (placement left), 2L-2 records; the centre
+ *   must be on site 0 and ends there.  amp_host / bx_host: those of the last bond.
+ * Refused: no attached state or more than one; a context with a communicator or an exchange hook; iDMRG windows; krylovdim
+ * outside 2..31.  An optimising htn_bond_update or a TDVP step on such a state does what it did before. */
+int htn_bond_solve(htn_mps* x, int32_t i, int32_t direction, int32_t placement, double z_re, double z_im, const htn_sweep_opts* opts,
+                   htn_bond_stats* stats_host, double* amp_host, double* bx_host);
+int htn_cv_sweep(htn_mps* x, double z_re, double z_im, const htn_sweep_opts* opts, htn_bond_stats* stats_host, double* amp_host,
+                 double* bx_host);
 
 /* Excited states inside one sector: orthogonalised two-site DMRG.  After htn_mps_set_orthogonal(mps, others, n) every
  * OPTIMISING bond update of `mps` finds the lowest eigenpair of H_eff inside the orthogonal complement of the n attached
