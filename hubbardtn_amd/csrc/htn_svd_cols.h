@@ -14,7 +14,8 @@
 //     otherwise in global memory (L2 resident: a few hundred KB);
 //   * sweeps stop early through the quadratic convergence of cyclic Jacobi: a sweep whose largest squared
 //     cosine, seen BEFORE the rotations, is below 0.1 tol leaves less than tol^2 behind, so neither the
-//     textbook's final "checking" sweep nor the sweep before it is run.
+//     textbook's final "checking" sweep nor the sweep before it is run -- unless the sweep rotated by large angles
+//     (columns of nearly equal norm: clustered singular values), where the cosines carry over at first order.
 #define JAC_THREADS 1024
 #define JAC_MAXEL 8           // column elements per lane kept in registers: m <= GS * JAC_MAXEL
 
@@ -32,7 +33,7 @@ __device__ __forceinline__ double group_sum(double v) {      // all-reduce insid
 template <int GS>
 __device__ __forceinline__ double jacobi_pair(double2* ga, double2* gb, double2* __restrict__ va,
                                               double2* __restrict__ vb, int m, int n, int sub, double tol,
-                                              bool accumulate, double zero2) {
+                                              bool accumulate, double zero2, double& t2max) {
     double2 a[JAC_MAXEL], b[JAC_MAXEL];
     double aa = 0.0, bb = 0.0, gr = 0.0, gi = 0.0;
 #pragma unroll
@@ -66,6 +67,7 @@ __device__ __forceinline__ double jacobi_pair(double2* ga, double2* gb, double2*
     const double w = w2 * fast_rsq(w2);
     double t = 2.0 * g * fast_rcp(fabs(h) + w);
     t = h >= 0.0 ? t : -t;
+    t2max = fmax(t2max, t * t);                       // largest tan^2 of the sweep's rotations, see jacobi_last_sweep
     const double c = fast_rsq(fma(t, t, 1.0));
     const double s = c * t;
     // b~ = exp(-i phi) b with exp(i phi) = gamma / |gamma|;  a' = c a - s b~ ; b' = s a + c b~
@@ -89,6 +91,18 @@ __device__ __forceinline__ double jacobi_pair(double2* ga, double2* gb, double2*
     return ratio2;
 }
 
+// Was this sweep the last?  mx: the largest SQUARED cosine it saw before its rotations, t2: the largest tan^2 it rotated by.
+// By the quadratic convergence of cyclic Jacobi a sweep leaves about C mx^2 behind (C = 0.005 .. 0.2 measured on
+// Schmidt-type spectra), so one that saw nothing above 0.1 tol has left < tol^2: no checking sweep afterwards.  That
+// argument needs SMALL rotation angles.  A rotation by tan t turns the cosines its two columns have with every other
+// column into each other at first order, t^2 mx squared: inside a cluster of singular values (s_i = 1 + i 1e-13: squared
+// cosines of 1e-24, angles of order one) the sweep leaves what it saw, and the column norms miss the singular values by
+// as much.  So the shortcut also asks for t2 mx <= tol^2; mx <= tol^2 alone means that nothing was rotated at all.
+__device__ __forceinline__ bool jacobi_last_sweep(double mx, double t2, double tol) {
+    const double tol2 = tol * tol;
+    return mx <= tol2 || (mx <= 0.1 * tol && t2 * mx <= tol2);
+}
+
 template <int GS>
 __device__ __forceinline__ int jacobi_sweeps(double2* g, double2* __restrict__ v, int m, int n, int max_sweeps,
                                              double tol, double* s_ratio, int tid, bool accumulate, double zero2) {
@@ -98,9 +112,9 @@ __device__ __forceinline__ int jacobi_sweeps(double2* g, double2* __restrict__ v
     int sweeps = 0;
     bool done = (n < 2);
     while (!done && sweeps < max_sweeps) {
-        if (tid == 0) *s_ratio = 0.0;
+        if (tid == 0) s_ratio[0] = s_ratio[1] = 0.0;
         __syncthreads();
-        double ratio = 0.0;
+        double ratio = 0.0, t2 = 0.0;
         for (int r = 0; r < np - 1; ++r) {
             for (int p = grp; p < np / 2; p += ngroups) {
                 int i, j;
@@ -114,7 +128,7 @@ __device__ __forceinline__ int jacobi_sweeps(double2* g, double2* __restrict__ v
                 if (i < n && j < n) {
                     const int lo = i < j ? i : j, hi = i < j ? j : i;
                     const double rr = jacobi_pair<GS>(g + (int64_t)lo * m, g + (int64_t)hi * m, v + (int64_t)lo * n,
-                                                      v + (int64_t)hi * n, m, n, sub, tol, accumulate, zero2);
+                                                      v + (int64_t)hi * n, m, n, sub, tol, accumulate, zero2, t2);
                     ratio = rr > ratio ? rr : ratio;
                 }
             }
@@ -122,13 +136,11 @@ __device__ __forceinline__ int jacobi_sweeps(double2* g, double2* __restrict__ v
         }
         // workgroup max of the non-negative ratio: doubles order like their bit patterns
         if (sub == 0 && ratio > 0.0) atomicMax((unsigned long long*)s_ratio, (unsigned long long)__double_as_longlong(ratio));
+        if (sub == 0 && t2 > 0.0) atomicMax((unsigned long long*)(s_ratio + 1), (unsigned long long)__double_as_longlong(t2));
         __syncthreads();
-        const double mx = *s_ratio;  // max over the sweep of the SQUARED cosine between column pairs
+        const double mx = s_ratio[0];  // max over the sweep of the SQUARED cosine between column pairs
         ++sweeps;
-        // mx is what the sweep SAW before its rotations; by the quadratic convergence of cyclic Jacobi the sweep
-        // leaves about C mx^2 behind (C = 0.005 .. 0.2 measured on Schmidt-type spectra).  A sweep that saw
-        // no squared cosine above 0.1 tol has therefore left < tol^2: no checking sweep afterwards.
-        done = mx <= fmax(tol * tol, 0.1 * tol);
+        done = jacobi_last_sweep(mx, s_ratio[1], tol);
         __syncthreads();
     }
     return done ? sweeps : -sweeps;
@@ -150,7 +162,7 @@ struct SplitCols {
 // of each column: no per-element predication, all loads issued back to back, and the LDS / global address
 // space is known at compile time (ds_* / global_* instead of flat_*).
 template <int GS, int E, typename P>
-__device__ __forceinline__ double jacobi_pair_pad(P ga, P gb, int sub, double tol2, double zero2) {
+__device__ __forceinline__ double jacobi_pair_pad(P ga, P gb, int sub, double tol2, double zero2, double& t2max) {
     double2 a[E], b[E];
     double aa = 0.0, bb = 0.0, gr = 0.0, gi = 0.0;
 #pragma unroll
@@ -181,6 +193,7 @@ __device__ __forceinline__ double jacobi_pair_pad(P ga, P gb, int sub, double to
     const double w = w2 * fast_rsq(w2);
     double t = 2.0 * g * fast_rcp(fabs(h) + w);
     t = h >= 0.0 ? t : -t;
+    t2max = fmax(t2max, t * t);                       // largest tan^2 of the sweep's rotations, see jacobi_last_sweep
     const double c = fast_rsq(fma(t, t, 1.0));
     const double s = c * t;
     // a' = c a - sig b ; b' = conj(sig)... written with sig = s exp(-i phi), tau = c exp(-i phi):
@@ -211,9 +224,9 @@ __device__ __forceinline__ int jacobi_sweeps_pad(C cols, int n, int max_sweeps, 
     int sweeps = 0;
     bool done = (n < 2);
     while (!done && sweeps < max_sweeps) {
-        if (tid == 0) *s_ratio = 0.0;
+        if (tid == 0) s_ratio[0] = s_ratio[1] = 0.0;
         __syncthreads();
-        double ratio = 0.0;
+        double ratio = 0.0, t2 = 0.0;
         for (int r = 0; r < md; ++r) {
             for (int p = grp; p < np / 2; p += ngroups) {
                 int i, j;
@@ -228,17 +241,18 @@ __device__ __forceinline__ int jacobi_sweeps_pad(C cols, int n, int max_sweeps, 
                 }
                 if (i < n && j < n) {
                     const int lo = i < j ? i : j, hi = i < j ? j : i;
-                    const double rr = jacobi_pair_pad<GS, E>(cols.col(lo), cols.col(hi), sub, tol2, zero2);
+                    const double rr = jacobi_pair_pad<GS, E>(cols.col(lo), cols.col(hi), sub, tol2, zero2, t2);
                     ratio = rr > ratio ? rr : ratio;
                 }
             }
             __syncthreads();
         }
         if (sub == 0 && ratio > 0.0) atomicMax((unsigned long long*)s_ratio, (unsigned long long)__double_as_longlong(ratio));
+        if (sub == 0 && t2 > 0.0) atomicMax((unsigned long long*)(s_ratio + 1), (unsigned long long)__double_as_longlong(t2));
         __syncthreads();
-        const double mx = *s_ratio;  // max over the sweep of the SQUARED cosine between column pairs
+        const double mx = s_ratio[0];  // max over the sweep of the SQUARED cosine between column pairs
         ++sweeps;
-        done = mx <= fmax(tol2, 0.1 * tol);                // quadratic convergence, see jacobi_sweeps
+        done = jacobi_last_sweep(mx, s_ratio[1], tol);
         __syncthreads();
     }
     return done ? sweeps : -sweeps;

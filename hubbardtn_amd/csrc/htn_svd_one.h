@@ -8,7 +8,7 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_svd(double2* __restrict_
                                                             int lds_elems, const int* __restrict__ large_slot,
                                                             double cut2) {
     extern __shared__ double2 g_lds[];
-    __shared__ double s_ratio;
+    __shared__ double s_ratio[2];      // |G|_F^2 first; then per sweep: largest squared cosine seen | largest tan^2 rotated by
     __shared__ double s_piv[2];
     __shared__ int s_col[64 * JAC_MAXEL];
     __shared__ double s_cn2[64 * JAC_MAXEL];
@@ -51,23 +51,23 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_svd(double2* __restrict_
             if (tid == 0) {
                 double t = 0.0;
                 for (int q = 0; q < JAC_THREADS / 64; ++q) t += s_cn2[q];
-                s_ratio = t;
+                s_ratio[0] = t;
             }
             __syncthreads();
         }
-        const double zero2q = 1e-30 * s_ratio;
+        const double zero2q = 1e-30 * s_ratio[0];
         __syncthreads();
         int swq;
         if (x_lds) {        // everything in LDS: ds_* addressing
             const DenseCols<double2*> dc = {(double2*)g_lds, mp};
-            if (gsx == 16) swq = jacobi_dispatch_e<16>(dc, E, rank, max_sweeps, tol, &s_ratio, tid, zero2q);
-            else if (gsx == 32) swq = jacobi_dispatch_e<32>(dc, E, rank, max_sweeps, tol, &s_ratio, tid, zero2q);
-            else swq = jacobi_dispatch_e<64>(dc, E, rank, max_sweeps, tol, &s_ratio, tid, zero2q);
+            if (gsx == 16) swq = jacobi_dispatch_e<16>(dc, E, rank, max_sweeps, tol, s_ratio, tid, zero2q);
+            else if (gsx == 32) swq = jacobi_dispatch_e<32>(dc, E, rank, max_sweeps, tol, s_ratio, tid, zero2q);
+            else swq = jacobi_dispatch_e<64>(dc, E, rank, max_sweeps, tol, s_ratio, tid, zero2q);
         } else {            // everything in global memory (L2 resident): global_* addressing
             const DenseCols<double2*> dc = {v, mp};
-            if (gsx == 16) swq = jacobi_dispatch_e<16>(dc, E, rank, max_sweeps, tol, &s_ratio, tid, zero2q);
-            else if (gsx == 32) swq = jacobi_dispatch_e<32>(dc, E, rank, max_sweeps, tol, &s_ratio, tid, zero2q);
-            else swq = jacobi_dispatch_e<64>(dc, E, rank, max_sweeps, tol, &s_ratio, tid, zero2q);
+            if (gsx == 16) swq = jacobi_dispatch_e<16>(dc, E, rank, max_sweeps, tol, s_ratio, tid, zero2q);
+            else if (gsx == 32) swq = jacobi_dispatch_e<32>(dc, E, rank, max_sweeps, tol, s_ratio, tid, zero2q);
+            else swq = jacobi_dispatch_e<64>(dc, E, rank, max_sweeps, tol, s_ratio, tid, zero2q);
         }
         __syncthreads();
         // column norms + write back with the pivoting undone: row k of X is row s_col[k] of the result
@@ -108,16 +108,16 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi_svd(double2* __restrict_
         if (tid == 0) {
             double t = 0.0;
             for (int q = 0; q < JAC_THREADS / 64; ++q) t += s_cn2[q];
-            s_ratio = t;
+            s_ratio[0] = t;
         }
         __syncthreads();
     }
-    const double zero2 = 1e-30 * s_ratio;
+    const double zero2 = 1e-30 * s_ratio[0];
     __syncthreads();
     int sw;
-    if (m <= 16 * JAC_MAXEL) sw = jacobi_sweeps<16>(g, v, m, n, max_sweeps, tol, &s_ratio, tid, accumulate, zero2);
-    else if (m <= 32 * JAC_MAXEL) sw = jacobi_sweeps<32>(g, v, m, n, max_sweeps, tol, &s_ratio, tid, accumulate, zero2);
-    else sw = jacobi_sweeps<64>(g, v, m, n, max_sweeps, tol, &s_ratio, tid, accumulate, zero2);
+    if (m <= 16 * JAC_MAXEL) sw = jacobi_sweeps<16>(g, v, m, n, max_sweeps, tol, s_ratio, tid, accumulate, zero2);
+    else if (m <= 32 * JAC_MAXEL) sw = jacobi_sweeps<32>(g, v, m, n, max_sweeps, tol, s_ratio, tid, accumulate, zero2);
+    else sw = jacobi_sweeps<64>(g, v, m, n, max_sweeps, tol, s_ratio, tid, accumulate, zero2);
     __syncthreads();
     // column norms (+ write back; the QR path undoes the pivoting: row k of X is row s_col[k] of the result)
     for (int j = wave; j < n; j += nwaves) {

@@ -552,6 +552,7 @@ __device__ __forceinline__ double ring_intra(double2* T, int nt, double2* B, int
     const int npT = nt + (nt & 1), npB = nb + (nb & 1), hT = npT >> 1, hB = npB >> 1;
     const int steps = (npT > npB ? npT : npB) - 1;
     double ratio = 0.0;
+    double t2_unused = 0.0;      // (the ring keeps the stopping rule without the rotation angles: only k_jacobi_svd reads them)
     for (int r = 0; r < steps; ++r) {
         double2* base = nullptr;
         int np = 0, pn = 0, p = 0;
@@ -569,7 +570,7 @@ __device__ __forceinline__ double ring_intra(double2* T, int nt, double2* B, int
             }
             if (i < pn && j < pn) {
                 const int lo = i < j ? i : j, hi = i < j ? j : i;
-                const double rr = jacobi_pair_pad<GS, E>(base + lo * mp, base + hi * mp, sub, tol2, zero2);
+                const double rr = jacobi_pair_pad<GS, E>(base + lo * mp, base + hi * mp, sub, tol2, zero2, t2_unused);
                 ratio = rr > ratio ? rr : ratio;
             }
         }

@@ -229,7 +229,10 @@ int htn_krylov_combine2_z(void* V, int64_t ldv, int32_t m, const double* y_host,
  * for the large blocks, no QR preconditioning (more outer sweeps); it runs on `stream` after the other blocks and needs
  * desc_host (without it m_i > 512 is an error).  Every other block must have max(m_i, pad_i) <= 512.
  * info_dev[i] receives the sweep count (<0: not converged).  A sweep ends the iteration when the largest squared
- * cosine it SAW before rotating was <= max(tol^2, 0.1 tol) (quadratic convergence: it leaves < tol^2 behind). */
+ * cosine it SAW before rotating was <= max(tol^2, 0.1 tol) (quadratic convergence: it leaves < tol^2 behind).  The blocks
+ * that one workgroup takes whole (every block inside the LDS window, every block of a call without desc_host) also ask that
+ * (largest tan^2 the sweep rotated by) x (that cosine^2) <= tol^2, unless nothing was rotated: inside a cluster of
+ * singular values the angles are of order one and a sweep leaves the cosines it saw. */
 #define HTN_SVD_ACCUMULATE 1      /* flags: also accumulate the rotation J (else Vj is not touched) */
 #define HTN_SVD_QRCP 2            /* flags: the block at g_off is G0 (pad x m, ld = pad); pivoted-QR precondition it,
                                      run Jacobi on R^H (m x n, n = min(pad, m)) and write the m x n result

@@ -212,5 +212,8 @@ class NumpyOps:
             f = np.full((rows, cols), gscale)
             if int(it["scale_dim"]) >= 0 and int(it["scl_off"]) >= 0:
                 sv = scl[int(it["scl_off"]) + (gi if int(it["scale_dim"]) == 0 else gj)]
-                f = f / sv if int(it["inv_norm"]) else f * sv
+                if int(it["inv_norm"]):      # a scale value that is not positive gives 0, like the libraries
+                    f = np.where(sv > 0.0, f / np.where(sv > 0.0, sv, 1.0), 0.0)
+                else:
+                    f = f * sv
             dst[int(it["dst_off"]) + i + j * int(it["ldd"])] = v * f
