@@ -147,6 +147,35 @@ class FiniteMPS:
 
 
 @dataclass
+class ThermalMPS(FiniteMPS):
+    """purified thermal state of n_phys physical sites on a chain of L = 2 n_phys sites (physical site i at 2 i, its ancilla at
+    2 i + 1; `thermal_state`, `cool`): |psi_beta> ~ exp(-beta H' / 2)|I>, normalised; log_z = ln Z(beta) of the grand-canonical
+    ensemble H - mu N the model defines.  The observables of this module report its physical sites only."""
+    n_phys: int = 0
+    beta: float = 0.0
+    log_z: float = 0.0
+    seeded: bool = False        # cool() has put the first bond directions into the beta = 0 tables (SEED_STEPS)
+
+
+SEED_STEPS = (1e-10, 1e-5)      # imaginary-time lengths of the two sweeps that open the bond tables of the beta = 0 state
+
+
+def _phys(psi, x):
+    """the physical sublattice of a per-site vector or a site x site matrix of a ThermalMPS; anything else unchanged"""
+    if not isinstance(psi, ThermalMPS):
+        return x
+    if isinstance(x, tuple):
+        return tuple(_phys(psi, v) for v in x)
+    return x[::2] if np.ndim(x) == 1 else x[::2, ::2]
+
+
+def _no_thermal(psi, what):
+    if isinstance(psi, ThermalMPS):
+        raise NotImplementedError(f"{what} of a ThermalMPS is not available: dynamics at finite temperature needs the bra of the "
+                                  "purification evolved as well")
+
+
+@dataclass
 class Environments:
     engine: object
 
@@ -363,6 +392,101 @@ def time_evolve(psi: FiniteMPS, H, times, alg, observe=None):
     return {"times": np.array(times), "energy": np.array([r["energy"] for r in out]),
             "density_state": np.array([r["n"] for r in out]), "double_occupancy": np.array([r["d"] for r in out]),
             "loschmidt": np.array([r["echo"] for r in out]), "trunc_weight": np.array([r["tw"] for r in out])}
+
+
+# ---- finite temperature: purified thermal states cooled by two-site TDVP -----------------------------------------------
+def _refuse_sharded(ops, what):
+    if bool(getattr(ops, "_cb", None)) or int(getattr(ops, "comm_world", 1)) > 1:
+        raise NotImplementedError(f"{what}: thermal states are not available in a context with a communicator or an exchange "
+                                  "hook")
+
+
+def thermal_state(simul: Simulation, L: int | None = None, ops=None):
+    """the infinite-temperature state of `simul` on L unit cells as a ThermalMPS at beta = 0: the purified chain of
+    mps.infinite_temperature_mps with models.purified_hamiltonian attached.  The ancillas carry the complementary
+    charge, so the physical particle number fluctuates at fixed chain charge: the ensemble is grand canonical and `mu` of the
+    model (the diagonal of t for MB_Sim) sets the filling; P / Q are not used."""
+    L = L or simul.kwargs.get("L")
+    if L is None:
+        raise NotImplementedError("thermal_state needs a chain length: thermal states live on a finite chain (pass L=)")
+    ops = ops or _ops()
+    _refuse_sharded(ops, "thermal_state")
+    H = models.purified_hamiltonian(simul, int(L))
+    n_phys = len(H) // 2
+    bonds, tensors = mps.infinite_temperature_mps(n_phys, H.sym)
+    eng = _engine.DMRG2(ops, H, bonds, tensors)
+    return ThermalMPS(eng, len(H), n_phys, 0.0, n_phys * float(np.log(4.0)))
+
+
+def cool(psi: ThermalMPS, betas, alg, dbeta: float = 0.05, observe=None):
+    """cool a ThermalMPS through the increasing list `betas` (the first not below psi.beta) by two-site TDVP steps in imaginary
+    time, alg = TDVP2(trscheme, ...): one tdvp_sweep(-i h / 2) per step of h = min(dbeta, gap to the next requested beta), so
+    every requested beta is hit exactly.  psi is advanced in place to betas[-1]; a second call continues from there.
+    With observe: the list of observe(psi, beta).  Without: a dict of arrays over the betas -- "betas", "energy" (<H'> of the
+    state at beta: one H_eff2 apply on bond 0), "log_z" (n_phys ln 4 + 2 sum of the sweeps' log_norm), "grand_potential"
+    (-log_z / beta; nan at beta = 0), "entropy" (beta (E - Omega); log_z at beta = 0), "density" and "double_occupancy"
+    ([len(betas), n_phys], one correlator pass each) and "trunc_weight" (discarded weight of the steps that led to each beta).
+    The first step from beta = 0 begins with the two sweeps of SEED_STEPS (each at most a quarter of that step), which open the
+    bond tables; they count in beta, so the step sizes above hold for their sum with the rest of the first step.
+    One-site TDVP() is refused: the bond tables of the beta = 0 state have dimension 1 and one-site steps never grow them."""
+    if not isinstance(psi, ThermalMPS):
+        raise TypeError("cool takes the ThermalMPS of thermal_state (an InfiniteMPS or a ground state has no temperature to lower)")
+    if isinstance(alg, TDVP):
+        raise TypeError("cool takes alg = TDVP2(...): the bond tables of the beta = 0 state have dimension 1, and one-site TDVP "
+                        "never grows them")
+    if not isinstance(alg, TDVP2):
+        raise TypeError("cool takes alg = TDVP2(...)")
+    _refuse_sharded(psi.engine.ops, "cool")
+    betas = [float(b) for b in np.atleast_1d(betas)]
+    dbeta = float(dbeta)
+    if dbeta <= 0.0:
+        raise ValueError("cool: dbeta must be positive")
+    if any(b1 <= b0 for b0, b1 in zip(betas[:-1], betas[1:])) or betas[0] < psi.beta:
+        raise ValueError(f"cool: betas must increase and start at or above the state's beta = {psi.beta}")
+    eng = _tdvp_setup(psi, None, alg)
+    out = []
+
+    def step(h):
+        k0 = len(eng.stats)
+        eng.tdvp_sweep(-0.5j * h)
+        psi.log_z += 2.0 * eng.log_norm
+        return float(sum(s.trunc_weight for s in eng.stats[k0:]))
+    for b in betas:
+        tw, seeded = 0.0, 0.0
+        if not psi.seeded and b - psi.beta > 1e-12:
+            # the beta = 0 tables have dimension 1 between rungs: a term that crosses two such bonds is invisible to every
+            # two-site projection there, and the first step would lose it -- an error of first order in dbeta (DESIGN 4g).  Two
+            # sweeps of negligible length put the bond directions of H'|I> and H'^2|I> into the tables first; they count as
+            # imaginary time, and the first regular step is shorter by their length.  Neither is ever left out: where the first
+            # step is itself that short, each takes a quarter of it at the most
+            first = min(dbeta, b - psi.beta)
+            for eps in SEED_STEPS:
+                eps = min(eps, 0.25 * first)
+                tw += step(eps)
+                seeded += eps
+            psi.beta += seeded
+            psi.seeded = True
+        while b - psi.beta > 1e-12:
+            gap = b - psi.beta
+            last = gap <= (dbeta - seeded) * (1.0 + 1e-9)   # (the sum of the steps so far carries rounding: the last one closes the gap)
+            h = gap if last else dbeta - seeded
+            seeded = 0.0
+            tw += step(h)
+            psi.beta = b if last else psi.beta + h
+        psi.beta = b
+        if observe is not None:
+            out.append(observe(psi, b))
+            continue
+        E = eng.centre_energy()
+        omega = -psi.log_z / b if b > 0.0 else float("nan")
+        out.append({"E": E, "lz": psi.log_z, "om": omega, "S": b * (E - omega) if b > 0.0 else psi.log_z,
+                    "n": density_state(psi), "d": double_occupancy(psi), "tw": tw})
+    if observe is not None:
+        return out
+    return {"betas": np.array(betas), "energy": np.array([r["E"] for r in out]), "grand_potential": np.array([r["om"] for r in out]),
+            "entropy": np.array([r["S"] for r in out]), "log_z": np.array([r["lz"] for r in out]),
+            "density": np.array([r["n"] for r in out]), "double_occupancy": np.array([r["d"] for r in out]),
+            "trunc_weight": np.array([r["tw"] for r in out])}
 
 
 def compute_groundstate(simul: Simulation, L: int | None = None, tol: float = 1e-6, verbosity: int = 0,
@@ -590,6 +714,8 @@ def density_state(psi):
         T = psi.result.unit_cell
         n, _ = psi.result.engine.site_occupations()
         return n[T // 2:T // 2 + T]
+    if isinstance(psi, ThermalMPS):
+        return _phys(psi, psi.engine.site_expectation("n"))
     return psi.engine.site_occupations()[0]
 
 
@@ -602,6 +728,10 @@ def density_spin(psi):
         T = psi.result.unit_cell
         up, dn = psi.result.engine.spin_occupations()
         return up[T // 2:T // 2 + T], dn[T // 2:T // 2 + T]
+    if isinstance(psi, ThermalMPS):
+        if psi.engine.sym.su2:
+            raise ValueError("This system is spin independent.")                # the reference's error text (src:1424)
+        return _phys(psi, (psi.engine.site_expectation("n_up"), psi.engine.site_expectation("n_dn")))
     return psi.engine.spin_occupations()
 
 
@@ -621,6 +751,8 @@ def double_occupancy(psi):
     if isinstance(psi, InfiniteMPS):
         T = psi.result.unit_cell
         return psi.result.engine.site_occupations()[1][T // 2:T // 2 + T]
+    if isinstance(psi, ThermalMPS):
+        return _phys(psi, psi.engine.site_expectation("docc"))
     return psi.engine.site_occupations()[1]
 
 
@@ -631,7 +763,7 @@ def correlation_function(psi, kind, connected=False):
     if isinstance(psi, InfiniteMPS):
         raise NotImplementedError("correlation functions need a chain length: they are measured on a finite chain "
                                   "(pass L= / use a FiniteMPS), not on an InfiniteMPS")
-    return psi.engine.correlator(kind, connected=connected)
+    return _phys(psi, psi.engine.correlator(kind, connected=connected))
 
 
 def structure_factor(psi, kind, q, connected=True):
@@ -662,6 +794,7 @@ def apply_operator(psi, name, site):
     if isinstance(psi, InfiniteMPS):
         raise NotImplementedError("apply_operator needs a chain length: operators are applied to a finite chain "
                                   "(pass L= / use a FiniteMPS), not to an InfiniteMPS")
+    _no_thermal(psi, "apply_operator")
     if not 0 <= int(site) < psi.L:
         raise ValueError(f"apply_operator: site {site} out of range (the chain has {psi.L} sites)")
     work = psi.engine.copy()
@@ -681,6 +814,7 @@ def greens_function(psi0, H, times, alg, op="c+", site=None):
     (TDVP2 of this library), so a truncating trscheme shows up in trunc_weight, not as a loss of norm."""
     if isinstance(psi0, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
         raise NotImplementedError("greens_function needs a chain length: it is measured on a finite chain, not on an InfiniteMPS")
+    _no_thermal(psi0, "greens_function")
     L = psi0.L
     site = L // 2 if site is None else int(site)
     times = [float(t) for t in times]
@@ -746,6 +880,7 @@ def correction_vector(psi0, H, omegas, eta, alg, op="c+", site=None, part="parti
     residual of the last sweep's solves), "trunc_weight" (largest discarded weight of the last sweep), "site", "eta"}"""
     if isinstance(psi0, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
         raise NotImplementedError("correction_vector needs a chain length: it is solved on a finite chain, not on an InfiniteMPS")
+    _no_thermal(psi0, "correction_vector")
     if not isinstance(alg, CorrectionVector):
         raise TypeError("correction_vector takes alg = CorrectionVector(...)")
     if part not in ("particle", "hole"):
@@ -819,6 +954,7 @@ def energy_variance(psi, H=None):
     if isinstance(psi, InfiniteMPS) or isinstance(H, InfiniteHamiltonian):
         raise NotImplementedError("energy_variance needs a chain length: it is measured on a finite chain "
                                   "(pass L= / use a FiniteMPS), not on an InfiniteMPS")
+    _no_thermal(psi, "energy_variance")
     eng = psi.engine
     if H is not None and H is not eng.mpo and H is not eng.cmpo:
         eng.set_mpo(H)

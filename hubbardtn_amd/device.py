@@ -65,6 +65,7 @@ class HipOps:
             dist.broadcast_object_list(box, src=0, group=group)
             ident = (C.c_char * 128).from_buffer_copy(box[0])
         abi.check(self.lib, self.lib.htn_ctx_set_comm(self.ctx, rank, world, ident), "htn_ctx_set_comm")
+        self.comm_world = int(world)
 
     def set_exchange(self, rank: int, world: int, fn):
         """caller-supplied reduction: fn(y_ptr, n) must enqueue/perform the sum of y (n complex128 at device pointer

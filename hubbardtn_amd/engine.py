@@ -374,6 +374,23 @@ class DMRG2:
         self._check(self.lib.htn_heff2_apply(self.handle, i, x.ctypes.data, y.ctypes.data), "htn_heff2_apply")
         return y
 
+    def centre_energy(self):
+        """<psi|H|psi> / <psi|psi> of the state as stored, read where the centre is when that is site 0 (after construction
+        and after every sweep): one H_eff2 apply on bond 0 and a dot product of two host vectors; theta of bond 0 has left
+        dimension 1, so both are tiny.  Nothing moves and nothing is decomposed (bond_energies costs a pass of SVD moves)."""
+        if self.centre() != 0:
+            raise ValueError("DMRG2.centre_energy: the centre must be on site 0")
+        th = self.theta(0)
+        return float(np.real(np.vdot(th, self.apply_heff(0, th))) / np.real(np.vdot(th, th)))
+
+    def site_expectation(self, name):
+        """ndarray[L]: <O_i> of the scalar site operator `name` ("n", "docc", spinful mode "n_up", "sz", ...) on every site by one
+        correlator pass on the device; the state is only read (any centre position).  The pass is a full one -- the L x L
+        channel with `name` as its one-site entry, of which only the diagonal is kept -- so a call costs what correlator() costs
+        per channel: the C interface has no entry that measures the diagonal alone."""
+        M, _ = self.correlator_channel(name, "id", name, name)
+        return np.real(np.diag(M)).copy()
+
     def plan_apply_dump(self, i, stage):
         """(tiles, segs, z_size, flops) of the H_eff apply on bond i as the kernels receive them (tests)"""
         nt, nsg, zs, fl = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)

@@ -604,8 +604,10 @@ def symmetry_of(sim) -> Symmetry:
     return U1U1 if bool(sim.kwargs.get("spin", False)) else SU2U1
 
 
-def hamiltonian(sim: Simulation, L: int):
-    """Reduced open-chain MPO over L unit cells (L*B sites).  Returns MPO (a list of MPOSite with `.sym`)."""
+def model_terms(sim: Simulation, L: int):
+    """the term list of the model on an open chain of L unit cells -> (nsites, onsite, pairs, strings), the arguments of
+    `_build_mpo`: onsite {site: [(opname, coef)]}, pairs [(i, j, kind, coef)] with i < j, strings the operator strings of the
+    `U112` / `U1111` terms of MB_Sim (empty for every other model)"""
     sym = symmetry_of(sim)
     if isinstance(sim, OB_Sim):
         if sim.period != 0:
@@ -619,7 +621,7 @@ def hamiltonian(sim: Simulation, L: int):
                 pairs += [(i, i + sim.period, "hop", -sim.t[0]) for i in range(L - sim.period)]
             else:                                        # period 1: the two terms coincide, -2 t on every bond
                 pairs = [(i, i + 1, "hop", -2.0 * sim.t[0]) for i in range(L - 1)]
-            return _build_mpo(L, onsite, pairs, sym)
+            return L, onsite, pairs, []
         onsite = {s: [("docc", sim.u[0]), ("n", -sim.mu)] for s in range(L)}          # src:424
         J_inter, Ms = (float(x) for x in sim.kwargs.get("JMs", (0.0, 0.0)))
         if Ms != 0.0 and sym is U1U1:                                                 # staggered field, src:459-463
@@ -639,7 +641,7 @@ def hamiltonian(sim: Simulation, L: int):
             for i in range(L - r):
                 _assisted_hop(pairs, i, i + r, float(Ur))
                 _assisted_hop(pairs, i + r, i, float(Ur))
-        return _build_mpo(L, onsite, pairs, sym)
+        return L, onsite, pairs, []
     if isinstance(sim, MB_Sim):
         B = sim.bands
         t, u, Jm = sim.t, sim.u, sim.J
@@ -745,5 +747,25 @@ def hamiltonian(sim: Simulation, L: int):
                             strings.append((U, _jw_string([(o(j), nj, False), (o(l), X.T, True), (o(i), X, True)])))
                     else:                          # j == l: C3 + C3'
                         _hop_product(strings, 0.5 * U, o(j), o(k), o(i), o(j))
-        return _build_mpo(n, onsite, pairs, sym, strings=strings)
+        return n, onsite, pairs, strings
     raise TypeError(f"unsupported simulation type {type(sim)}")
+
+
+def hamiltonian(sim: Simulation, L: int):
+    """Reduced open-chain MPO over L unit cells (L*B sites).  Returns MPO (a list of MPOSite with `.sym`)."""
+    nsites, onsite, pairs, strings = model_terms(sim, L)
+    return _build_mpo(nsites, onsite, pairs, symmetry_of(sim), strings=strings)
+
+
+def purified_hamiltonian(sim: Simulation, L: int):
+    """H' of the purified (ancilla-doubled) chain of a thermal state: the model's terms on the physical sublattice of a chain
+    of twice as many sites -- physical site s at 2 s, its ancilla at 2 s + 1, nothing on the ancillas.  The Jordan-Wigner
+    pass operators of the hopping channels run across the ancillas like across any site in between; every ancilla parity
+    commutes with H', and a gauge that is diagonal in the occupation basis removes the signs they leave.  Models
+    with `U112` / `U1111` strings are refused: a string is a product over a contiguous range of sites."""
+    nsites, onsite, pairs, strings = model_terms(sim, L)
+    if strings:
+        raise NotImplementedError("purified_hamiltonian: the U112 / U1111 operator strings of MB_Sim cover contiguous sites and "
+                                  "have no form with ancillas in between")
+    return _build_mpo(2 * nsites, {2 * s: list(v) for s, v in onsite.items()},
+                      [(2 * i, 2 * j, kind, coef) for (i, j, kind, coef) in pairs], symmetry_of(sim))

@@ -53,6 +53,38 @@ def random_mps(nsites, target, max_dimension, seed=1234, max_twoS=6, sym=SU2U1):
     return bonds, tensors
 
 
+def infinite_temperature_mps(n_phys, sym=SU2U1):
+    """the beta = 0 state of a purified chain: n_phys rungs (physical site at 2 i, ancilla at 2 i + 1), every rung in
+    1/2 sum_s |s>|s-bar> with s-bar the complementary site state (N -> 2 - N, the spins coupled to a singlet), so that the
+    physical density matrix is 1 / 4^n_phys and every rung lies in the sector (N = 2, S = 0).  Bond tables: one sector of
+    count 1 between rungs, one multiplet per site multiplet inside a rung (in the SU(2) kind without U(1) the empty and the
+    doubly occupied state share the label (0, 0): count 2).  The amplitude of site multiplet s is sqrt(dim(s) / 4); signs
+    inside a rung are an ancilla unitary and left at +.  Same return convention as random_mps (right-canonical, centre on
+    site 0, tilde normalisation): total sector (2 n_phys, 0), or (0, 0) without U(1)."""
+    ns = sym.n_site
+    bonds, tensors = [{(0, 0): 1}], []
+    for i in range(n_phys):
+        left, right = (sym.wrap(2 * i), 0), (sym.wrap(2 * i + 2), 0)
+        mid, row = {}, {}
+        for s in range(ns):
+            (c,) = sym.fuse(left, s)                # (the left sector has spin 0: one way to fuse)
+            row[s] = mid.get(c, 0)
+            mid[c] = row[s] + 1
+        phys, anc = {}, {}
+        for s in range(ns):
+            (c,) = sym.fuse(left, s)
+            sbar = ns - 1 - s                       # empty <-> double, single <-> single (up <-> down in the spinful mode)
+            assert right in sym.fuse(c, sbar)
+            P = np.zeros((1, mid[c]))
+            P[0, row[s]] = np.sqrt(sym.qdim(sym.site_mult[s]) / 4.0)
+            A = np.zeros((mid[c], 1))
+            A[row[s], 0] = 1.0
+            phys[(left, s, c)], anc[(c, sbar, right)] = P, A
+        bonds += [mid, {right: 1}]
+        tensors += [phys, anc]
+    return bonds, tensors
+
+
 def random_window(nsites, bond_left, bond_right, max_dimension, seed=1234, max_twoS=8, sym=SU2U1):
     """random state of `nsites` sites between two FIXED boundary bond tables (the bases of the left and right
     environment blocks of an iDMRG window, hubbardtn_amd/idmrg.py).  Internal virtual spaces = sectors reachable
