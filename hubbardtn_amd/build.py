@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 # htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
 # unit on purpose (bit-identical host arithmetic, see its head).  Do not list those files here: every symbol would be defined twice.
+# htn_plan.cpp does the same with the planner: htn_recouple.cpp, htn_layout.cpp, htn_balance.cpp and the htn_plan_*.cpp files.
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("htn_abi.hip", "htn_gemm.hip", "htn_krylov.hip", "htn_svd.hip", "htn_qr.hip", "htn_measure.hip", "htn_place.hip", "htn_nullproj.hip",
                                                 "htn_backend_hip.hip", "htn_plan.cpp", "htn_engine.cpp")]
 LIB = os.path.join(HERE, "csrc", "libhubbardtn_hip.so")
@@ -20,7 +21,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    # (every header, and every .cpp: htn_engine.cpp includes the files the engine is split into)
+    # (every header, and every .cpp: htn_plan.cpp and htn_engine.cpp include the files the planner and the engine are split into)
     deps = SRCS + glob.glob(os.path.join(HERE, "csrc", "*.h")) + glob.glob(os.path.join(HERE, "csrc", "*.cpp")) + [os.path.join(INC, "hubbardtn_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

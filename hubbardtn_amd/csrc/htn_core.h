@@ -1,6 +1,6 @@
 // Host-side core of the two-site DMRG engine: sector layouts, recoupling coefficients, the contraction compiler
-// (sector tables + reduced MPO -> htn_tile / htn_seg task lists), the global truncation rule and the bond-update /
-// sweep driver.  Pure C++17, no HIP: the same translation units are linked into libhubbardtn_hip.so (device work =
+// (sector tables + reduced MPO -> htn_tile / htn_seg task lists), the global truncation rule (htn_plan.cpp and the files it
+// includes; the assembler of the task lists is htn_tasks.h) and the bond-update / sweep driver (htn_engine.cpp).  Pure C++17, no HIP: the same translation units are linked into libhubbardtn_hip.so (device work =
 // hand-written gfx950 kernels through htn::Backend) and into the CPU baseline library built from oracle/cpu_backend.
 //
 // Stands in for what TensorKit 0.14.6 (fusion trees, tree transformers, tsvd!, truncation), KrylovKit 0.9.5 (eigsolve)
@@ -214,10 +214,6 @@ struct Tasks {
     std::vector<htn_seg> segs;
     int32_t nsegs = 0;
     int64_t flops = 0;           // algorithmic complex128 flops (8 per MAC) of the GEMM segments
-    // optional placement hint for balance_tiles: ascending start offsets (in the output buffer) of groups of output blocks
-    // whose tiles read the same operands (H_eff apply: one group per coupled-sector matrix of theta); tiles of a group are
-    // steered to one XCD so that its L2 fetches those operands once.  Empty: tiles are grouped by output row strip.
-    std::vector<int64_t> group_bounds;
 };
 
 // Load balance of one grouped-GEMM launch (HIP backend): the launch is bound by its longest tile's dependent K loop,

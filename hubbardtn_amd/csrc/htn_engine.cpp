@@ -10,8 +10,8 @@
 // update step by step.  The rest of the host core sits in one file per concern and is compiled as part of
 // THIS translation unit (included below): htn_backend_host.cpp (host statements of Backend methods), htn_site.cpp (one-site
 // updates, time evolution), htn_overlap.cpp (overlaps, attached states, correlators), htn_applyop.cpp (local operators applied to a state), htn_variance.cpp (the two-site energy variance), htn_idmrg.cpp (the infinite-chain growth
-// loop), htn_capi.cpp (the C entry points).  One unit on purpose: a build line names htn_plan.cpp and this file, as it always
-// did, and g++ -O3 contracts the same fused multiply-adds in the host arithmetic as before the split -- across separate units
+// loop), htn_capi.cpp (the C entry points).  One unit on purpose: a build line names htn_plan.cpp (the planner, which includes
+// its own parts in the same way) and this file, as it always did, and g++ -O3 contracts the same fused multiply-adds in the host arithmetic as before the split -- across separate units
 // the CPU baseline library changes its last bits (profiles/r07_engine_refactor_identity.txt, r09_engine_split_identity.txt).
 // Host C++ (no HIP): device work goes through htn::Backend.
 #include "htn_engine.h"

@@ -1,6 +1,6 @@
 """Builds oracle/cpu_backend/libhubbardtn_cpu.so: the CPU baseline / checker behind the same C ABI as the product
 (see htn_backend_cpu.cpp).  g++ + OpenMP; the planner and sweep-driver sources are the product's own
-(the host sources of hubbardtn_amd/csrc: htn_plan.cpp, htn_engine.cpp and the files it includes), only the kernels differ."""
+(the host sources of hubbardtn_amd/csrc: htn_plan.cpp, htn_engine.cpp and the files they include), only the kernels differ."""
 from __future__ import annotations
 
 import glob
@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "hubbardtn_amd", "csrc")
 # htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
 # unit on purpose (bit-identical host arithmetic, see its head).  Do not list those files here: every symbol would be defined twice.
+# htn_plan.cpp does the same with the planner: htn_recouple.cpp, htn_layout.cpp, htn_balance.cpp and the htn_plan_*.cpp files.
 SRCS = [os.path.join(CSRC, "htn_plan.cpp"), os.path.join(CSRC, "htn_engine.cpp"), os.path.join(HERE, "htn_backend_cpu.cpp")]
 LIB = os.path.join(HERE, "libhubbardtn_cpu.so")
 
@@ -21,7 +22,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    # (every header, and every .cpp: htn_engine.cpp includes the files the engine is split into)
+    # (every header, and every .cpp: htn_plan.cpp and htn_engine.cpp include the files the planner and the engine are split into)
     deps = SRCS + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.cpp")) + [os.path.join(ROOT, "include", "hubbardtn_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

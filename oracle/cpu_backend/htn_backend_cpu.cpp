@@ -1,6 +1,6 @@
 // CPU BASELINE / CHECKER (test + benchmark infrastructure; the product never loads this).
 //
-// libhubbardtn_cpu.so = the SAME host core as the product (hubbardtn_amd/csrc/htn_plan.cpp, htn_engine.cpp and the files around it: sector
+// libhubbardtn_cpu.so = the SAME host core as the product (hubbardtn_amd/csrc/htn_plan.cpp, htn_engine.cpp and the files they include: sector
 // layouts, 9j recoupling, task lists, truncation, sweep driver) linked against THIS file instead of the HIP kernels:
 // a plain C++/OpenMP execution of the task lists on host memory.  It is the CPU comparator SURVEY.md 8(d) and
 // BASELINE.md section 4 specify ("the build's own CPU backend behind the same C ABI: task-parallel over

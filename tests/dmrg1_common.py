@@ -52,7 +52,7 @@ def converge_onesite(e, max_sweeps=12):
 
 
 def gauge_block_shapes(e, i, direction):
-    """[(m, n)] of the blocks the gauge move of update_site(i, direction) factorises (plan_gauge1 of htn_plan.cpp: one
+    """[(m, n)] of the blocks the gauge move of update_site(i, direction) factorises (plan_gauge1 of htn_plan_env.cpp: one
     sector matrix per right sector of the centre, its (l, s) blocks stacked, for direction +1; per left sector, the (s, r)
     blocks side by side and m their total width, for -1) -- from the stored blocks of the centre, before the move"""
     assert e.centre() == i

@@ -11,6 +11,7 @@ import pytest
 
 import ref_planner as pl
 from cpu_ops import CpuOps
+from gemm_cases import poly_model as _poly
 from hubbardtn_amd import abi, api, engine, models, mps, storage
 from oracle import dmrg_su2, ed, mpo as ompo
 
@@ -21,13 +22,6 @@ E_ED_L8_U4 = -4.235806999130
 @pytest.fixture(scope="module")
 def cpu_ops():
     return CpuOps()
-
-
-def _poly():
-    t = np.array([[0.000, 3.803, -0.548, 0.000], [3.803, 0.000, 2.977, -0.501]])
-    U = np.array([[10.317, 6.264, 0.000, 0.000], [6.264, 10.317, 6.162, 0.000]])
-    J = np.array([[0.000, 0.123, 0.000, 0.000], [0.123, 0.000, 0.113, 0.000]])
-    return models.MB_Sim(t, U, J, 1, 1, 2.5, 20)
 
 
 @pytest.mark.parametrize("model", ["nn", "nnn_nn", "exchange", "poly"])

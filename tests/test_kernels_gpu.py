@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from emul import NumpyOps
+from gemm_cases import random_tasks as _random_tasks
 from hubbardtn_amd import abi
 from ref_planner import TaskList
 
@@ -15,34 +16,6 @@ pytestmark = pytest.mark.gpu
 
 def _rand_z(rng, n):
     return rng.standard_normal(n) + 1j * rng.standard_normal(n)
-
-
-def _random_tasks(rng, nblocks, maxdim, maxk, nbuf_elems):
-    """random grouped-GEMM problem exercising all ops, ragged sizes, COPY segments, empty blocks"""
-    tl = TaskList()
-    out_off = 0
-    for b in range(nblocks):
-        m, n = int(rng.integers(1, maxdim)), int(rng.integers(1, maxdim))
-        ld = m + int(rng.integers(0, 3))
-        tl.block(b, 1, out_off, m, n, ld)
-        out_off += ld * n
-        for s in range(int(rng.integers(0, 5))):
-            alpha = complex(rng.standard_normal(), rng.standard_normal())
-            if rng.random() < 0.2:
-                ldb = m + int(rng.integers(0, 4))
-                off = int(rng.integers(0, nbuf_elems - ldb * n - 1))
-                tl.copy(b, 0, off, ldb, alpha)
-                continue
-            k = int(rng.integers(1, maxk))
-            op_a, op_b = int(rng.integers(0, 3)), int(rng.integers(0, 3))
-            lda = (m if op_a == abi.OP_N else k) + int(rng.integers(0, 3))
-            ldb = (k if op_b == abi.OP_N else n) + int(rng.integers(0, 3))
-            sa = lda * (k if op_a == abi.OP_N else m)
-            sb = ldb * (n if op_b == abi.OP_N else k)
-            a_off = int(rng.integers(0, nbuf_elems - sa - 1))
-            b_off = int(rng.integers(0, nbuf_elems - sb - 1))
-            tl.gemm(b, 0, a_off, lda, op_a, 2, b_off, ldb, op_b, k, alpha)
-    return tl.finalize(), out_off
 
 
 @pytest.mark.parametrize("seed,nblocks,maxdim,maxk", [(0, 40, 20, 30), (1, 25, 75, 90), (2, 6, 140, 300)])
