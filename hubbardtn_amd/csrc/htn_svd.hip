@@ -22,7 +22,11 @@
 //   QRCP with more than 512 rows                                   refused
 //
 // Pair visits and tall visits share the tournament (jacobi_tournament), the sweep pipeline (jacobi_sweep_pipeline) and the
-// 16 x 16 Gram-visit core (jg_* in htn_svd_visits.h).  htn_batched_copy.h (k_batched_copy, htn_batched_copy_z) is unrelated
+// 16 x 16 Gram-visit core (jg_* in htn_svd_visits.h).  Every path stops its sweeps by ONE rule, jacobi_last_sweep
+// (htn_svd_cols.h), from two numbers per block and sweep: the largest squared cosine the sweep saw before its rotations and
+// the largest tan^2 it rotated by -- kept in LDS by the one-workgroup kernel, in two 64-bit words per block by the visits
+// (integer maxima on the bit patterns, read and zeroed by k_jacobi_check) and by the ring (its sync block).
+// htn_batched_copy.h (k_batched_copy, htn_batched_copy_z) is unrelated
 // to the SVD and only lives in this unit.
 #include <algorithm>
 #include <utility>
@@ -255,7 +259,7 @@ struct JacCoreBufs {
     // device: [large_ids | slot of every block | perm | zero2 | ratio | done | sweeps | qsync | items]
     int *d_ids, *d_slot, *d_perm;
     double* d_zero;
-    unsigned long long* d_ratio;
+    unsigned long long* d_ratio;      // per block: [largest squared cosine | largest tan^2] of the sweep, as bits
     int *d_done, *d_sw;
     unsigned* d_qsync;           // QR_SYNC_WORDS per block + failure word
     JacPairItem* d_items;
@@ -270,7 +274,7 @@ struct JacCoreBufs {
 static int carve_core_scratch(JacScratch& js, int nl, int n_blocks, int max_sweeps, size_t n_items_max, JacCoreBufs* B) {
     const size_t off_ids = 0, off_slot = off_ids + sizeof(int) * nl, off_perm = off_slot + sizeof(int) * n_blocks;
     const size_t off_zero = off_perm + sizeof(int) * nl * 64 * JAC_MAXEL;
-    const size_t off_ratio = (off_zero + sizeof(double) * nl + 7) / 8 * 8, off_done = off_ratio + 8 * nl;
+    const size_t off_ratio = (off_zero + sizeof(double) * nl + 7) / 8 * 8, off_done = off_ratio + 16 * nl;      // ratio: 2 words per block
     const size_t off_sw = off_done + sizeof(int) * nl, off_qsync = off_sw + sizeof(int) * nl;
     const size_t off_items = (off_qsync + sizeof(unsigned) * (QR_SYNC_WORDS * (size_t)nl + 8) + 31) / 32 * 32;
     if (js.dev.reserve(off_items + sizeof(JacPairItem) * n_items_max)) return 1;
@@ -414,11 +418,11 @@ static int run_ring(const JacCall& c, JacScratch& js, const JacCoreBufs& B, cons
                     bool staged_send, int32_t* sweeps_used) {
     const int nl = c.nl(), n_wg = plan.wgs, n_items = (int)plan.items.size();
     // sync block (32-bit words): [flags: 2 per workgroup | arrivals: nl x max_sweeps | failure word | XCD ids: 1 per
-    // workgroup | pad] then the 64-bit maxima, nl x max_sweeps; zeroed as ONE block that starts its allocation and is a
-    // multiple of 16 bytes
+    // workgroup | pad] then the 64-bit maxima, 2 x nl x max_sweeps; zeroed as ONE block that starts its allocation and is a
+    // multiple of 16 bytes.  Two maxima per block and sweep: squared cosine, tan^2 (jacobi_last_sweep).
     const int arrive_off = 2 * n_wg, fail_off = arrive_off + nl * c.max_sweeps, xcc_off = fail_off + 1;
     const int conv_off = (xcc_off + n_wg + 3) & ~3;
-    const size_t sync_bytes = ((size_t)conv_off * 4 + (size_t)nl * c.max_sweeps * 8 + 15) & ~(size_t)15;
+    const size_t sync_bytes = ((size_t)conv_off * 4 + (size_t)nl * c.max_sweeps * 16 + 15) & ~(size_t)15;
     if (js.ring_sync.reserve(sync_bytes)) return 1;
     if (js.ring_mbox.reserve(sizeof(double2) * (size_t)std::max<int64_t>(plan.mbox_elems, 1))) return 1;
     if (js.ring_items.reserve(sizeof(RingItem) * n_items) || js.ring_items_h.reserve(sizeof(RingItem) * n_items)) return 1;
@@ -466,13 +470,12 @@ static int run_pair_visits(const JacCall& c, JacScratch& js, const JacCoreBufs& 
     int max_mp = 0;
     for (int b : c.large) max_mp = std::max(max_mp, jac_padded_rows(c.desc_host[b].m));
     const size_t gram_lds_bytes = (size_t)(16 * (max_mp + 1) + JG_GU_ELEMS) * sizeof(double2);
-    const double thr = std::max(c.tol * c.tol, 0.1 * c.tol);          // quadratic convergence, see jacobi_sweeps
     const int used = jacobi_sweep_pipeline(c.max_sweeps, hint, js.ev_sweep, B.h_active, c.st, [&](int sweep) {
         for (int r = 0; r < T.n_rounds(); ++r)
             if (T.round_size(r))
                 hipLaunchKernelGGL(k_jacobi_pairs_gram, dim3(T.round_size(r)), dim3(256), gram_lds_bytes, c.st, c.Vj, c.desc,
                                    B.d_ids, B.d_items + T.off[r], B.d_zero, B.d_ratio, B.d_done, c.tol, 1);
-        hipLaunchKernelGGL(k_jacobi_check, dim3(1), dim3(64), 0, c.st, B.d_ratio, B.d_done, B.d_sw, nl, thr, B.d_active + sweep);
+        hipLaunchKernelGGL(k_jacobi_check, dim3(1), dim3(64), 0, c.st, B.d_ratio, B.d_done, B.d_sw, nl, c.tol, B.d_active + sweep);
     });
     if (used < 0) return 1;
     if (sweeps_used) *sweeps_used = used;
@@ -525,7 +528,7 @@ static int jacobi_svd_core(void* G, void* Vj, double* S, const htn_svd_block* de
     // every small copy / fill is a separate blit launch on the stream: they are enqueued BEFORE the QR (nothing here
     // depends on it unless a rank cut sizes the tournament), merged where the regions are contiguous
     HIP_TRY(hipMemcpyAsync(B.d_ids, B.h_ids, sizeof(int) * (nl + n_blocks), hipMemcpyHostToDevice, c.st));
-    HIP_TRY(hipMemsetAsync(B.d_ratio, 0, 16 * (size_t)nl + sizeof(unsigned) * (QR_SYNC_WORDS * (size_t)nl + 8), c.st));      // ratio (8 nl) | done (4 nl) | sweeps (4 nl) | qsync
+    HIP_TRY(hipMemsetAsync(B.d_ratio, 0, 24 * (size_t)nl + sizeof(unsigned) * (QR_SYNC_WORDS * (size_t)nl + 8), c.st));      // ratio (16 nl) | done (4 nl) | sweeps (4 nl) | qsync
     // Ring path (default): all sweeps of the large blocks in one launch per batch of <= #CU workgroups.  The multi-launch
     // pair-visit path stays for blocks the ring cannot take (more CU slots than the chip has) and behind HTN_SVD_PAIRS=1.
     static const bool force_pairs = htn_env_flag("HTN_SVD_PAIRS");
@@ -589,7 +592,7 @@ static int jacobi_svd_tall(void* G, void* Vj, double* S, const htn_svd_block* de
     // device scratch [skip | ids | zero2 | partials | ratio | done | sweeps | items]; ratio | done | sweeps zeroed as one
     const size_t off_skip = 0, off_ids = off_skip + sizeof(int) * n_blocks;
     const size_t off_zero = (off_ids + sizeof(int) * nt + 7) / 8 * 8, off_part = off_zero + sizeof(double) * nt;
-    const size_t off_ratio = off_part + sizeof(double) * nt * TALL_PARTS, off_done = off_ratio + 8 * (size_t)nt;
+    const size_t off_ratio = off_part + sizeof(double) * nt * TALL_PARTS, off_done = off_ratio + 16 * (size_t)nt;      // ratio: 2 words per block
     const size_t off_sw = off_done + sizeof(int) * nt, off_items = (off_sw + sizeof(int) * nt + 31) / 32 * 32;
     const size_t flag_elems = (size_t)std::max(max_sweeps, 0) + 1;
     if (js.tall_dev.reserve(off_items + sizeof(JacPairItem) * std::max<size_t>(n_items, 1))) return 1;
@@ -616,7 +619,7 @@ static int jacobi_svd_tall(void* G, void* Vj, double* S, const htn_svd_block* de
     for (size_t k = 0; k < flag_elems; ++k) h_active[k] = 1;
     HIP_TRY(hipMemcpyAsync(d_skip, h_skip, sizeof(int) * (n_blocks + nt), hipMemcpyHostToDevice, st));
     if (upload_tournament(T, h_items, d_items, st)) return 1;
-    HIP_TRY(hipMemsetAsync(d_ratio, 0, 16 * (size_t)nt, st));      // ratio (8 nt) | done (4 nt) | sweeps (4 nt)
+    HIP_TRY(hipMemsetAsync(d_ratio, 0, 24 * (size_t)nt, st));      // ratio (16 nt) | done (4 nt) | sweeps (4 nt)
     // everything else first: small blocks, QRCP large blocks (their call returns once they are done)
     int core_used = 0;
     if (nt < n_blocks) {
@@ -630,14 +633,13 @@ static int jacobi_svd_tall(void* G, void* Vj, double* S, const htn_svd_block* de
     hipLaunchKernelGGL(k_jacobi_tall_init, dim3(nt, TALL_PARTS), dim3(256), 0, st, (double2*)G, (double2*)Vj, desc, d_ids, d_part);
     hipLaunchKernelGGL(k_jacobi_tall_zero, dim3(1), dim3(64), 0, st, (const double*)d_part, d_zero, nt);
     HIP_TRY(hipGetLastError());
-    const double thr = std::max(tol * tol, 0.1 * tol);
     const int hint = opts && opts->sweeps_hint > 0 ? opts->sweeps_hint : 0;
     const int used = jacobi_sweep_pipeline(max_sweeps, hint, js.ev_sweep, h_active, st, [&](int sweep) {
         for (int r = 0; r < T.n_rounds(); ++r)
             if (T.round_size(r))
                 hipLaunchKernelGGL(k_jacobi_tall_visit, dim3(T.round_size(r)), dim3(TALL_THREADS), 0, st, (double2*)G,
                                    (double2*)Vj, desc, d_ids, d_items + T.off[r], d_zero, d_ratio, d_done, tol);
-        hipLaunchKernelGGL(k_jacobi_check, dim3(1), dim3(64), 0, st, d_ratio, d_done, d_sw, nt, thr, d_active + sweep);
+        hipLaunchKernelGGL(k_jacobi_check, dim3(1), dim3(64), 0, st, d_ratio, d_done, d_sw, nt, tol, d_active + sweep);
     });
     if (used < 0) return 1;
     hipLaunchKernelGGL(k_jacobi_tall_finish, dim3((unsigned)((max_n + 3) / 4), (unsigned)nt), dim3(256), 0, st,

@@ -299,9 +299,12 @@ struct RingStamps {
 // OUT = true (the round's last step when the columns leave from registers): b' goes, times its final scale, to column offset
 // out_off of the mailbox slot out_rs instead of to b_out, and `sent` is set; a pair that is not rotated leaves `sent` alone
 // and the caller sends b as it stands.  The same multiply-adds on the same operands.
+// sec2max <- max(sec2max, 1 + tan^2 of this rotation): 1 + q^2 |g|^2 is the argument of the rsq that gives c, so the second
+// number of the stopping rule (jacobi_last_sweep) costs one v_max_f64 per rotation.  tan^2 = sec2max - 1 resolves 2e-16,
+// and the rule compares tan^2 with tol^2 / mx >= 1e-13 (it is asked only where mx <= 0.1 tol).
 template <int GS, int E, bool OUT = false>
 __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const double2 (&b)[E], double2* b_out, double& aa, double& bb,
-                                                     double& sa, double& sb, double tol2, double zero2, RingStamps& st,
+                                                     double& sa, double& sb, double tol2, double zero2, double& sec2max, RingStamps& st,
                                                      __amdgpu_buffer_rsrc_t out_rs = __amdgpu_buffer_rsrc_t(), int out_off = 0,
                                                      bool out_local = false, bool* sent = nullptr) {
     // conj(a_st) * b_st in FOUR independent chains (even / odd elements x re / im): a dependent f64 multiply-add cannot issue
@@ -333,7 +336,9 @@ __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const doub
     const double w = w2 * __builtin_amdgcn_rsq(w2);
     double q = 2.0 * __builtin_amdgcn_rcp(fabs(h) + w);
     q = h >= 0.0 ? q : -q;
-    const double c = fast_rsq(fma(q * q, g2, 1.0));
+    const double sec2 = fma(q * q, g2, 1.0);
+    const double c = fast_rsq(sec2);
+    sec2max = fmax(sec2max, sec2);
     aa = fma(-q, g2, aa);
     bb = fma(q, g2, bb);
     const double qb = q * sb * sb, qa = q * sa * sa;
@@ -401,10 +406,11 @@ __device__ __forceinline__ double ring_rotate_scaled(double2 (&a)[E], const doub
 //     out.slot_b; group g < nt stores its T column to out.slot_t (send_t) and / or writes it to LDS (keep_t).  The bottom
 //     panel always leaves, so it is not written back to LDS, and there is no barrier here: the caller's drain + barrier
 //     before the flag is the next one.
+// Returns the largest squared cosine seen; sec2max <- max(sec2max, 1 + largest tan^2 rotated by), see ring_rotate_scaled.
 template <int GS, int E, bool TWO, bool SEND>
 __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int nb, int tid, double tol2, double zero2, double* bnorm,
                                              double* bscale, const double* tnorm, bool have_t, bool have_b, const RingOut& out,
-                                             long long* split) {
+                                             long long* split, double& sec2max) {
     static_assert(!TWO || GS == 16, "two partners per step need both rows of a pair in one wave");
     static_assert(!(TWO && SEND), "the two-partner step keeps the staged send");
     constexpr int mp = GS * E;
@@ -465,8 +471,8 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
                 for (int e = 0; e < E; ++e) b[e] = bc[GS * e];
                 double bb = bnorm[j], sb = bscale[j];
                 RING_ST(st, 1);
-                const double rr = ring_rotate_scaled<GS, E>(a, b, bc, aa, bb, sa, sb, tol2, zero2, st);
-                ratio = rr > ratio ? rr : ratio;
+                const double rr = ring_rotate_scaled<GS, E>(a, b, bc, aa, bb, sa, sb, tol2, zero2, sec2max, st);
+                ratio = fmax(ratio, rr);
                 if (sub == 0) {
                     bnorm[j] = bb;
                     bscale[j] = sb;
@@ -510,9 +516,9 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
             double bb = bnorm[jp], sb = bscale[jp];
             bool sent = false;
             if (own) {
-                const double rr = ring_rotate_scaled<GS, E, true>(a, b, nullptr, aa, bb, sa, sb, tol2, zero2, st, out.slot_b,
+                const double rr = ring_rotate_scaled<GS, E, true>(a, b, nullptr, aa, bb, sa, sb, tol2, zero2, sec2max, st, out.slot_b,
                                                                   jp * mp + sub, out.local, &sent);
-                ratio = rr > ratio ? rr : ratio;
+                ratio = fmax(ratio, rr);
             }
             if (!sent) ring_send_col<GS, E>(b, sb, out.slot_b, jp * mp + sub, out.local);
         }
@@ -546,13 +552,12 @@ __device__ __forceinline__ double ring_cross(double2* T, double2* B, int nt, int
 
 // the pairs inside each resident panel (circle tournament per panel, both panels side by side)
 template <int GS, int E>
-__device__ __forceinline__ double ring_intra(double2* T, int nt, double2* B, int nb, int tid, double tol2, double zero2) {
+__device__ __forceinline__ double ring_intra(double2* T, int nt, double2* B, int nb, int tid, double tol2, double zero2, double& t2max) {
     constexpr int mp = GS * E;
     const int grp = tid / GS, sub = tid % GS;
     const int npT = nt + (nt & 1), npB = nb + (nb & 1), hT = npT >> 1, hB = npB >> 1;
     const int steps = (npT > npB ? npT : npB) - 1;
     double ratio = 0.0;
-    double t2_unused = 0.0;      // (the ring keeps the stopping rule without the rotation angles: only k_jacobi_svd reads them)
     for (int r = 0; r < steps; ++r) {
         double2* base = nullptr;
         int np = 0, pn = 0, p = 0;
@@ -570,7 +575,7 @@ __device__ __forceinline__ double ring_intra(double2* T, int nt, double2* B, int
             }
             if (i < pn && j < pn) {
                 const int lo = i < j ? i : j, hi = i < j ? j : i;
-                const double rr = jacobi_pair_pad<GS, E>(base + lo * mp, base + hi * mp, sub, tol2, zero2, t2_unused);
+                const double rr = jacobi_pair_pad<GS, E>(base + lo * mp, base + hi * mp, sub, tol2, zero2, t2max);
                 ratio = rr > ratio ? rr : ratio;
             }
         }
@@ -597,7 +602,8 @@ struct RingArgs {
     const int* perm;
     const double* zero2;
     double2* mbox;
-    unsigned* sync;              // [flags: 2 per workgroup | arrive: nl * max_sweeps | fail | pad | conv (u64): nl * max_sweeps]
+    unsigned* sync;              // [flags: 2 per workgroup | arrive: nl * max_sweeps | fail | pad | conv (u64): 2 x nl * max_sweeps,
+                                 //  per block and sweep the largest squared cosine seen, then the largest tan^2 rotated by]
     int arrive_off, fail_off, conv_off;      // in 32-bit words (conv_off even)
     int xcc_off;                 // 32-bit words: one per workgroup, XCD id + 1 once the workgroup has started
     int max_sweeps;
@@ -621,7 +627,7 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     unsigned* flags = A.sync;
     unsigned* fail = A.sync + A.fail_off;
     const double zero2 = A.zero2[it.li];
-    const double tol2 = A.tol * A.tol, thr = fmax(tol2, 0.1 * A.tol);
+    const double tol2 = A.tol * A.tol;
     auto ncols = [&](int q) {
         const int c = n - q * w;
         return c < 0 ? 0 : (c > w ? w : c);
@@ -692,7 +698,7 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
     double* const s_bscale = s_bnorm + RING_THREADS / 16;
     double* const s_tnorm = s_bnorm + 2 * (RING_THREADS / 16);
     while (!done && ok && sweeps < A.max_sweeps) {
-        double ratio = 0.0;
+        double ratio = 0.0, t2 = 0.0, sec2 = 1.0;      // sec2: 1 + tan^2 of the cross rotations, t2: tan^2 of those inside the panels
         for (int r = 0; r < rounds && ok; ++r) {
             const unsigned epoch = (unsigned)(sweeps * rounds + r + 1);
             const int par = (int)(epoch & 1u);
@@ -714,11 +720,11 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
             out.slot_b = __builtin_amdgcn_make_buffer_rsrc((void*)to_b, 0, reg_send ? nb * mp * 16 : 0, 0x00020000);
             out.send_t = send_t, out.keep_t = !send_t, out.local = local;
             double rr = 0.0;
-            if (reg_send) rr = ring_cross<GS, E, false, true>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split);
+            if (reg_send) rr = ring_cross<GS, E, false, true>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split, sec2);
             else if (GS == 16 && A.two_partner) {
                 if constexpr (GS == 16)        // (64 lanes per column: the two rows of a pair would be two waves)
-                    rr = ring_cross<GS, E, true, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split);
-            } else rr = ring_cross<GS, E, false, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split);
+                    rr = ring_cross<GS, E, true, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split, sec2);
+            } else rr = ring_cross<GS, E, false, false>(bufT, bufB, nt, nb, tid, tol2, zero2, s_bnorm, s_bscale, s_tnorm, have_t, have_b, out, split, sec2);
             ratio = rr > ratio ? rr : ratio;
             JAC_T(RING_PROF, p1);
             JAC_ACC(RING_PROF, prof, 0, p0, p1);
@@ -804,37 +810,45 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
         if (!ok) break;
         JAC_T(RING_PROF, p5);
         {
-            const double rr = ring_intra<GS, E>(bufT, ncols(s_top[k]), bufB, ncols(s_bot[k]), tid, tol2, zero2);
+            const double rr = ring_intra<GS, E>(bufT, ncols(s_top[k]), bufB, ncols(s_bot[k]), tid, tol2, zero2, t2);
             ratio = rr > ratio ? rr : ratio;
         }
         JAC_T(RING_PROF, p6);
         JAC_ACC(RING_PROF, prof, 4, p5, p6);
-        // ---- block-wide maximum of the squared cosines this sweep SAW: one returning atomic max + one arrival per workgroup ----
-        if (tid == 0) *s_rbits = 0ull;
+        // ---- block-wide maxima of the squared cosines this sweep SAW and of the tan^2 it rotated by (integer maxima on the
+        //      bit patterns: any order gives the same bits): two returning atomic maxima + one arrival per workgroup ----
+        if (tid == 0) s_rbits[0] = s_rbits[1] = 0ull;
         __syncthreads();
         {
             const unsigned long long key = wave_max_u64((unsigned long long)__double_as_longlong(ratio));
+            const unsigned long long key2 = wave_max_u64((unsigned long long)__double_as_longlong(fmax(t2, sec2 - 1.0)));
             if (lane == 0 && key) atomicMax(s_rbits, key);
+            if (lane == 0 && key2) atomicMax(s_rbits + 1, key2);
         }
         __syncthreads();
         if (tid == 0) {
-            unsigned long long* conv = (unsigned long long*)(A.sync + A.conv_off) + (int64_t)it.li * A.max_sweeps + sweeps;
+            unsigned long long* conv = (unsigned long long*)(A.sync + A.conv_off) + 2 * ((int64_t)it.li * A.max_sweeps + sweeps);
             unsigned* arrive = A.sync + A.arrive_off + it.li * A.max_sweeps + sweeps;
-            unsigned long long mx = *s_rbits;
+            unsigned long long mx = s_rbits[0], mt = s_rbits[1];
             if (P > 1) {
                 const unsigned long long old = __hip_atomic_fetch_max(conv, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the maximum has been applied before this workgroup arrives
+                const unsigned long long old2 = __hip_atomic_fetch_max(conv + 1, mt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the maxima have been applied before this workgroup arrives
                 (void)old;
+                (void)old2;
                 __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (ring_wait_ge(arrive, (unsigned)P, fail)) mx = __hip_atomic_load(conv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else *s_ok = 0;
+                if (ring_wait_ge(arrive, (unsigned)P, fail)) {
+                    mx = __hip_atomic_load(conv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    mt = __hip_atomic_load(conv + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else *s_ok = 0;
             }
-            *s_rbits = mx;
+            s_rbits[0] = mx;
+            s_rbits[1] = mt;
         }
         __syncthreads();
         ok = *s_ok != 0;
         ++sweeps;
-        done = __longlong_as_double((long long)*s_rbits) <= thr;
+        done = jacobi_last_sweep(__longlong_as_double((long long)s_rbits[0]), __longlong_as_double((long long)s_rbits[1]), A.tol);
         __syncthreads();
         JAC_T(RING_PROF, p7);
         JAC_ACC(RING_PROF, prof, 5, p6, p7);
@@ -882,7 +896,7 @@ __device__ __forceinline__ void ring_run(const RingArgs A, const RingItem it, co
 __global__ __launch_bounds__(RING_THREADS) void k_jacobi_ring(RingArgs A) {
     extern __shared__ double2 g_lds[];
     __shared__ int s_top[RING_MAX_P], s_bot[RING_MAX_P];
-    __shared__ unsigned long long s_rbits;
+    __shared__ unsigned long long s_rbits[2];                // the sweep's largest squared cosine | largest tan^2, as bits
     __shared__ int s_ok, s_local;
     __shared__ double s_bnorm[3 * (RING_THREADS / 16)];      // tracked squared norms | scales of the bottom panel's columns | norms of a received top panel
     __shared__ unsigned s_arr[2];                            // direct receive: the epoch whose top / bottom panel has arrived
@@ -892,18 +906,18 @@ __global__ __launch_bounds__(RING_THREADS) void k_jacobi_ring(RingArgs A) {
     const int m = D.m;
     const int gs = ring_gs(m), E = ring_e(m);
 #define RING_CASE(GSV, EV) \
-    case EV: ring_run<GSV, EV>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local, s_arr); break;
+    case EV: ring_run<GSV, EV>(A, it, D, g_lds, s_top, s_bot, s_rbits, &s_ok, s_bnorm, &s_local, s_arr); break;
     if (gs == 16) {                  // m <= 256
         switch (E) {
             RING_CASE(16, 1) RING_CASE(16, 2) RING_CASE(16, 3) RING_CASE(16, 4) RING_CASE(16, 5) RING_CASE(16, 6) RING_CASE(16, 7)
             RING_CASE(16, 8) RING_CASE(16, 9) RING_CASE(16, 10) RING_CASE(16, 11) RING_CASE(16, 12) RING_CASE(16, 13)
             RING_CASE(16, 14) RING_CASE(16, 15)
-            default: ring_run<16, 16>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local, s_arr);
+            default: ring_run<16, 16>(A, it, D, g_lds, s_top, s_bot, s_rbits, &s_ok, s_bnorm, &s_local, s_arr);
         }
     } else {                         // 256 < m <= 512: E = 5 .. 8
         switch (E) {
             RING_CASE(64, 5) RING_CASE(64, 6) RING_CASE(64, 7)
-            default: ring_run<64, 8>(A, it, D, g_lds, s_top, s_bot, &s_rbits, &s_ok, s_bnorm, &s_local, s_arr);
+            default: ring_run<64, 8>(A, it, D, g_lds, s_top, s_bot, s_rbits, &s_ok, s_bnorm, &s_local, s_arr);
         }
     }
 #undef RING_CASE

@@ -5,8 +5,9 @@
 // A block whose R^H does not fit one CU's LDS is VALU-bound on that CU (all n/2 pairs of a round on 16
 // waves).  Here the columns are cut into panels of w = 8; one WORKGROUP handles one PAIR of panels (a "visit"),
 // the panel pairs of one tournament round run on different CUs, and rounds are separated by kernel boundaries
-// (the only cross-CU synchronisation used: no in-kernel grid barriers).  The host reads one number per block
-// and outer sweep (max squared cosine) to stop.
+// (the only cross-CU synchronisation used: no in-kernel grid barriers).  Per block and outer sweep the visits leave two
+// numbers, the largest squared cosine they saw and the largest tan^2 they rotated by; k_jacobi_check decides from them
+// with jacobi_last_sweep (htn_svd_cols.h), the one statement of the stopping rule, and the host reads one count per sweep.
 #define JAC_PANEL 8
 struct JacPairItem {
     int32_t blk, ci, ni, cj, nj, pad[3];
@@ -48,10 +49,10 @@ __device__ __forceinline__ double2 cmulc(double2 ac, double2 b) {      // conj(a
 
 
 // rotation that annihilates the (lo, hi) entry g of a 2 x 2 Hermitian pivot [[aa, g], [conj g, bb]]: c = cos, cq = cos *
-// tan / |g|, dq = tan * |g|; identity (returns false) for dead slots, numerically zero columns and pairs already
-// orthogonal to tol.  No branches: cos from cos(2 theta) = |h| / w runs in parallel with the reciprocal that gives q.
+// tan / |g|, dq = tan * |g|, t2 = tan^2; identity (returns false, t2 = 0) for dead slots, numerically zero columns and pairs
+// already orthogonal to tol.  No branches: cos from cos(2 theta) = |h| / w runs in parallel with the reciprocal that gives q.
 __device__ __forceinline__ bool jg_rotation(double aa, double bb, double2 g, bool live, double z2, double tol2,
-                                            double& c, double& cq, double& dq) {
+                                            double& c, double& cq, double& dq, double& t2) {
     const double g2 = fma(g.x, g.x, g.y * g.y);
     const bool on = live && aa > z2 && bb > z2 && g2 > 0.0 && g2 > tol2 * aa * bb;
     const double h = on ? bb - aa : 0.0, g2s = on ? g2 : 1.0, ah = fabs(h);
@@ -64,6 +65,7 @@ __device__ __forceinline__ bool jg_rotation(double aa, double bb, double2 g, boo
     c = on ? cc : 1.0;
     cq = on ? cc * q : 0.0;
     dq = on ? q * g2s : 0.0;
+    t2 = on ? q * q * g2s : 0.0;
     return on;
 }
 
@@ -105,7 +107,8 @@ __device__ __forceinline__ void jg_gram_store(double2* GU, double2 g, int ei, in
 }
 
 // convergence measure of a visit: max squared cosine over its column pairs (exact Gram), as bits, through s_rbits (zeroed
-// before the last barrier).  True: nothing to rotate in this visit (uniform), the measure has been handed to ratio_bits.
+// before the last barrier).  True: nothing to rotate in this visit (uniform), the measure has been handed to ratio_bits
+// (the block's first word: [2 blk] squared cosine, [2 blk + 1] tan^2, see jg_visit_report).
 __device__ __forceinline__ bool jg_visit_converged(const double2* GU, const JacPairItem& it, int mode, int ei, int ej, double z2,
                                                    double tol2, unsigned long long* s_rbits,
                                                    unsigned long long* ratio_bits, unsigned long long& first_bits) {
@@ -127,14 +130,23 @@ __device__ __forceinline__ bool jg_visit_converged(const double2* GU, const JacP
     return true;
 }
 
+// what a visit that rotated leaves for k_jacobi_check: the squared cosine it saw first and the largest tan^2 it rotated by,
+// integer maxima on the bit patterns (non-negative doubles order like their bits): the order of the visits does not matter
+__device__ __forceinline__ void jg_visit_report(unsigned long long* ratio_bits, int blk, unsigned long long first_bits, double t2max) {
+    const unsigned long long key = wave_max_u64((unsigned long long)__double_as_longlong(t2max));
+    if ((threadIdx.x & 63) == 0 && threadIdx.x < 256 && key) atomicMax(&ratio_bits[2 * blk + 1], key);
+    if (threadIdx.x == 0) atomicMax(&ratio_bits[2 * blk], first_bits);
+}
+
 // `inner` cyclic sweeps of two-sided Jacobi on G, U <- U J; returns the buffer (0 / 1) that holds the final G and U.
+// t2max <- the largest tan^2 among the rotations of this thread's row pairs (every pair of a round is some row's).
 // One thread per element (i, j).  It needs the rotation of i's pair (row operation) and of j's pair (column
 // operation) and computes both itself from the pivot entries -- 256-fold redundant arithmetic, but the
 // round is then a single chain [12 LDS reads -> two interleaved rotations -> update -> write] with ONE
 // barrier (G and U are double buffered), instead of [8 lanes rotate] barrier [256 lanes apply] barrier.
 template <bool MIRROR>
 __device__ __forceinline__ int jg_rounds(double2* GU, const JacPairItem& it, int mode, int inner, int ei, int ej, double z2,
-                                         double tol2) {
+                                         double tol2, double& t2max) {
     const int nrounds = mode ? 7 : 8;
     unsigned livemask = 0;
 #pragma unroll
@@ -158,9 +170,10 @@ __device__ __forceinline__ int jg_rounds(double2* GU, const JacPairItem& it, int
             const double2 uij = Uc[ei * JG_LD + ej], uijb = Uc[ei * JG_LD + jb];
             // J = [[c, c q g], [-c q conj(g), c]] on (lo, hi), q = tan / |g|: real diagonal, no phase division.
             // Both rotations are computed branch-free (jg_rotation) so that their two dependent chains interleave.
-            double ci, cqi, dqi, cj, cqj, dqj;
-            const bool oni = jg_rotation(iaa, ibb, ig, ((livemask >> ilo) & (livemask >> ihi) & 1u) != 0, z2, tol2, ci, cqi, dqi);
-            jg_rotation(jaa, jbb, jg, ((livemask >> jlo) & (livemask >> jhi) & 1u) != 0, z2, tol2, cj, cqj, dqj);
+            double ci, cqi, dqi, cj, cqj, dqj, t2i, t2j;
+            const bool oni = jg_rotation(iaa, ibb, ig, ((livemask >> ilo) & (livemask >> ihi) & 1u) != 0, z2, tol2, ci, cqi, dqi, t2i);
+            jg_rotation(jaa, jbb, jg, ((livemask >> jlo) & (livemask >> jhi) & 1u) != 0, z2, tol2, cj, cqj, dqj, t2j);
+            t2max = fmax(t2max, t2i);
             // column j of J: J[j][j] = c, J[jb][j] = -cq conj(g) if j is the lower index, +cq g if the upper
             const double2 jpj = ej == jlo ? make_double2(-cqj * jg.x, cqj * jg.y) : make_double2(cqj * jg.x, cqj * jg.y);
             const double2 ipi = ei == ilo ? make_double2(-cqi * ig.x, cqi * ig.y) : make_double2(cqi * ig.x, cqi * ig.y);
@@ -283,9 +296,10 @@ __global__ __launch_bounds__(256) void k_jacobi_pairs_gram(double2* __restrict__
     jg_gram_store<false>(GU, gij, ei, ej);
     __syncthreads();
     unsigned long long first_bits;
-    if (jg_visit_converged(GU, it, mode, ei, ej, z2, tol2, &s_rbits, &ratio_bits[it.blk], first_bits)) return;
+    if (jg_visit_converged(GU, it, mode, ei, ej, z2, tol2, &s_rbits, &ratio_bits[2 * it.blk], first_bits)) return;
     // ---- (2) two-sided Jacobi on G, U <- U J ----
-    const int cur = jg_rounds<false>(GU, it, mode, inner, ei, ej, z2, tol2);
+    double t2max = 0.0;
+    const int cur = jg_rounds<false>(GU, it, mode, inner, ei, ej, z2, tol2, t2max);
     // ---- (3) P <- P U, transposed product so that a lane's 16 neighbours write 256 contiguous bytes:
     //      D[b][i] = sum_a U[a][b] P[i][a]:  A operand U[4 kk + l4][l15], B operand P[i0 + l15][4 kk + l4] ----
     {
@@ -322,25 +336,28 @@ __global__ __launch_bounds__(256) void k_jacobi_pairs_gram(double2* __restrict__
                 if (colg[r] >= 0) X[(int64_t)colg[r] * mp + i0 + l15] = make_double2(ar[r], ai[r]);
         }
     }
-    if (tid == 0) atomicMax(&ratio_bits[it.blk], first_bits);
+    jg_visit_report(ratio_bits, it.blk, first_bits, t2max);
 }
 
 // after every outer sweep: convergence bookkeeping of the large blocks ON THE DEVICE (one thread per block), so
 // the host never has to answer before the next sweep can start.  active_out is host-pinned: the host reads it
 // one sweep late (the next sweep is already enqueued; if everything had converged its visits return at once).
+// ratio_bits: two words per block, the sweep's largest squared cosine and largest tan^2 (jg_visit_report); both are zeroed
+// here for the next sweep.
 __global__ void k_jacobi_check(unsigned long long* __restrict__ ratio_bits, int* __restrict__ done,
-                               int* __restrict__ sweeps, int nl, double thr, int* __restrict__ active_out) {
+                               int* __restrict__ sweeps, int nl, double tol, int* __restrict__ active_out) {
     __shared__ int s_active;
     if (threadIdx.x == 0) s_active = 0;
     __syncthreads();
     for (int li = threadIdx.x; li < nl; li += blockDim.x) {
         if (!done[li]) {
-            const double mx = __longlong_as_double((long long)ratio_bits[li]);
+            const double mx = __longlong_as_double((long long)ratio_bits[2 * li]);
+            const double t2 = __longlong_as_double((long long)ratio_bits[2 * li + 1]);
             sweeps[li] += 1;
-            if (mx <= thr) done[li] = 1;
+            if (jacobi_last_sweep(mx, t2, tol)) done[li] = 1;
             else atomicAdd(&s_active, 1);
         }
-        ratio_bits[li] = 0ull;
+        ratio_bits[2 * li] = ratio_bits[2 * li + 1] = 0ull;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -490,14 +507,15 @@ __global__ __launch_bounds__(TALL_THREADS) void k_jacobi_tall_visit(double2* __r
     jg_gram_store<true>(GU, jg_gram_element<TALL_WAVES>(s_part, ei, ej), ei, ej);
     __syncthreads();
     unsigned long long first_bits;
-    if (jg_visit_converged(GU, it, mode, ei, ej, z2, tol2, &s_rbits, &ratio_bits[it.blk], first_bits)) return;
+    if (jg_visit_converged(GU, it, mode, ei, ej, z2, tol2, &s_rbits, &ratio_bits[2 * it.blk], first_bits)) return;
     // ---- (b) two-sided Jacobi on G, U <- U J: one cyclic sweep ----
-    const int cur = jg_rounds<true>(GU, it, mode, 1, ei, ej, z2, tol2);
+    double t2max = 0.0;
+    const int cur = jg_rounds<true>(GU, it, mode, 1, ei, ej, z2, tol2, t2max);
     // ---- (c) X[:, pair] <- X[:, pair] U, and J[:, pair] <- J[:, pair] U when accumulating ----
     const double2* Uf = GU + (2 + cur) * 16 * JG_LD;
     tall_apply(X, m, m, Uf, it, wave, l15, l4);
     if (D.flags & HTN_SVD_ACCUMULATE) tall_apply(Vj + D.v_off, n, n, Uf, it, wave, l15, l4);
-    if (tid == 0) atomicMax(&ratio_bits[it.blk], first_bits);
+    jg_visit_report(ratio_bits, it.blk, first_bits, t2max);
 }
 
 // |X|_F^2 of every tall block in TALL_PARTS column stripes (fixed-order sums: bit-reproducible), J = identity when

@@ -142,11 +142,13 @@ def _rounds(n):
     return out
 
 
-def hestenes(M, dtype=np.clongdouble, tol=None, zero_rel=None, max_sweeps=60):
+def hestenes(M, dtype=np.clongdouble, tol=None, zero_rel=None, max_sweeps=60, stop=None):
     """cyclic one-sided Jacobi on the columns of M (of M^H when M is wide) in `dtype`: a pair is rotated when its squared
     cosine exceeds tol^2 (default 4 eps of dtype), sweeps go on until one has rotated nothing.  A column below
     zero_rel |M|_F (default 1000 eps) takes no part: it is the rounding residue of an exactly rank-deficient input and
-    has no direction; its norm, below that threshold, is still reported.  -> (column norms, descending; sweeps)"""
+    has no direction; its norm, below that threshold, is still reported.  -> (column norms, descending; sweeps)
+    stop(mx, t2) -> bool (the twins of the kernels' stopping rules, svd_large_cases.py): decides instead whether a sweep
+    was the last, from the largest squared cosine it saw before its rotations and the largest tan^2 it rotated by"""
     A = np.array(M, dtype=dtype)
     if A.shape[0] < A.shape[1]:
         A = A.conj().T.copy()
@@ -158,26 +160,31 @@ def hestenes(M, dtype=np.clongdouble, tol=None, zero_rel=None, max_sweeps=60):
     rounds = _rounds(n)
     for sweep in range(1, max_sweeps + 1):
         rotated = False
+        mx = t2 = real(0)
         for I, J in rounds:
             a, b = A[:, I], A[:, J]
             aa = (a.real ** 2 + a.imag ** 2).sum(axis=0)
             bb = (b.real ** 2 + b.imag ** 2).sum(axis=0)
             g = (a.conj() * b).sum(axis=0)
             g2 = g.real ** 2 + g.imag ** 2
-            k = np.nonzero((aa > zero2) & (bb > zero2) & (g2 > tol2 * aa * bb))[0]
+            live = (aa > zero2) & (bb > zero2)
+            if stop is not None and live.any():
+                mx = max(mx, (g2[live] / (aa[live] * bb[live])).max())
+            k = np.nonzero(live & (g2 > tol2 * aa * bb))[0]
             if len(k) == 0:
                 continue
             rotated = True
             ga = np.sqrt(g2[k])
             zeta = (bb[k] - aa[k]) / (2 * ga)
             t = np.where(zeta >= 0, real(1), real(-1)) / (np.abs(zeta) + np.sqrt(1 + zeta * zeta))
+            t2 = max(t2, (t * t).max())
             c = 1 / np.sqrt(1 + t * t)
             s = c * t
             bt = b[:, k] * (g[k] / ga).conj()           # a^H bt = |a^H b|: a real rotation finishes the pair
             ak = a[:, k]
             A[:, I[k]] = c * ak - s * bt
             A[:, J[k]] = s * ak + c * bt
-        if not rotated:
+        if stop(mx, t2) if stop is not None else not rotated:
             break
     else:
         raise AssertionError(f"hestenes: {max_sweeps} sweeps of a {A.shape} matrix in {np.dtype(dtype)} did not converge")
@@ -245,12 +252,13 @@ def pack(call):
     return P
 
 
-def run(ops, call, P=None):
-    """one htn_jacobi_svd_z call from fresh copies of the packed buffers -> (G, Vj, S, info on the host, return value)"""
+def run(ops, call, P=None, split=0, max_sweeps=MAX_SWEEPS):
+    """one htn_jacobi_svd_z call from fresh copies of the packed buffers -> (G, Vj, S, info on the host, return value).
+    split: htn_svd_opts.split_elems, the test mode that sends QRCP blocks below the window to the large-block path"""
     P = pack(call) if P is None else P
     dG, dV, dS, info = ops.to_device(P.G), ops.to_device(P.V), ops.to_device(P.S), ops.to_device(P.info)
-    used = ops.jacobi_svd(dG, dV, dS, ops.to_device(P.desc), len(call.blocks), P.max_m, MAX_SWEEPS, TOL, info,
-                          desc_host=P.desc if call.host else None)
+    used = ops.jacobi_svd(dG, dV, dS, ops.to_device(P.desc), len(call.blocks), P.max_m, max_sweeps, TOL, info,
+                          desc_host=P.desc if call.host else None, **({"split": split} if split else {}))
     return ops.to_host(dG), ops.to_host(dV), ops.to_host(dS), ops.to_host(info), used
 
 
@@ -307,12 +315,17 @@ def check_qrcp(b, out, s, ref, sig, bar):
     return dev
 
 
-def check(call, P, result, check_info=True, check_relative=True):
+def check(call, P, result, check_info=True, check_relative=True, large=False):
     """prints every figure, then asserts; -> {block name: (deviation / sigma_max, bar, sorted S)}.
     check_relative=False leaves out the one RELATIVE bound (S of an already orthogonal block to 4 eps of every entry): a
-    property of one-sided Jacobi that LAPACK, accurate to eps sigma_max, does not have"""
+    property of one-sided Jacobi that LAPACK, accurate to eps sigma_max, does not have.
+    large=True (svd_large_cases.py): the call is meant for the multi-workgroup paths, whose outer sweeps the return value
+    counts: it must be >= 1, and comes back beside the figures -> (figures, used)"""
     G, V, S, info, used = result
-    assert used in (0, None), (call.name, "the call left the one-workgroup kernel: outer sweeps of the large-block path", used)
+    if large:
+        assert used is not None and used >= 1, (call.name, "the call stayed in the one-workgroup kernel", used)
+    else:
+        assert used in (0, None), (call.name, "the call left the one-workgroup kernel: outer sweeps of the large-block path", used)
     _gaps_untouched("G", P.G, G, [(go, b.g_size) for (go, _, _), b in zip(P.regions, call.blocks)])
     _gaps_untouched("Vj", P.V, V, [(vo, b.v_size) for (_, vo, _), b in zip(P.regions, call.blocks)])
     _gaps_untouched("S", P.S, S, [(so, b.s_size) for (_, _, so), b in zip(P.regions, call.blocks)])
@@ -325,7 +338,7 @@ def check(call, P, result, check_info=True, check_relative=True):
             failures.append(e)
     if failures:
         raise failures[0]
-    return figs
+    return (figs, used) if large else figs
 
 
 def _check_block(call, b, k, go, vo, so, G, V, S, info, check_info, check_relative):
