@@ -172,7 +172,7 @@ def _phys(psi, x):
 def _no_thermal(psi, what):
     if isinstance(psi, ThermalMPS):
         raise NotImplementedError(f"{what} of a ThermalMPS is not available: dynamics at finite temperature needs the bra of the "
-                                  "purification evolved as well")
+                                  "purification evolved as well (thermal_greens_function evolves both)")
 
 
 @dataclass
@@ -941,6 +941,95 @@ def spectral_function_cv(res, q):
     ph = np.exp(-1j * qs[:, None] * (np.arange(L) - res["site"])[None, :])        # [q, x]
     A = -(ph @ G.T).imag / np.pi
     return A if np.ndim(q) else A[0]
+
+
+# ---- finite-temperature dynamics: both states of the purification evolved -----------------------------------------------
+def thermal_greens_function(psi, times, alg, op="c+", site=None):
+    """C[t, x] = <psi_beta| exp(+i K t) O+_x exp(-i K t) O_site |psi_beta> = Tr[rho_beta O+_x(t) O_site] of a ThermalMPS at its
+    current beta, for all n_phys physical sites x and the increasing list `times` (the first entry is the time of the applied
+    state itself, normally 0); site is a physical index, n_phys // 2 by default.  K is the Hamiltonian attached to the state
+    (models.purified_hamiltonian): the model including its -mu N, so ensemble and dynamics are grand canonical.  op: any name
+    engine.DMRG2.apply_op takes in the state's symmetry ("c+", "c", "n", "S", spinful mode "c+_up", ...); as in greens_function
+    the overlaps carry the sum over the components of the operator's multiplet: both spins for "c+" in the SU(2) modes,
+    <S_x(t) . S_site> for "S".
+    Method: the ancillas stay idle, so psi_beta is no eigenstate of K and the bra is evolved as well -- per interval one
+    tdvp_sweep on a copy of psi (the bra) and one on O_site psi (the ket; the operator is applied on chain site 2 site), alg =
+    TDVP2(...) for both, then one `transition` pass, of which the physical sublattice is kept.  The bra carries the phase that
+    greens_function removes with exp(+i E0 t): there is none here.  One-site TDVP() is refused.  psi itself is not touched.
+    -> {"times", "C": [len(times), n_phys] complex, "trunc_weight": [len(times), 2] (discarded weight of the step that led to each
+    time, bra and ket), "site", "beta", "op"}; spectral_function takes the result as it is, thermal_spectral_function a particle
+    and a hole result.  The factor -i and the step function are left to the caller, as for greens_function."""
+    if isinstance(psi, InfiniteMPS):
+        raise NotImplementedError("thermal_greens_function needs a chain length: thermal states live on a finite chain, not on an "
+                                  "InfiniteMPS")
+    if not isinstance(psi, ThermalMPS):
+        raise TypeError("thermal_greens_function takes the ThermalMPS of thermal_state / cool; the Green's function of a ground "
+                        "state is greens_function")
+    if isinstance(alg, TDVP):
+        raise TypeError("thermal_greens_function takes alg = TDVP2(...): one-site TDVP never leaves the bond tables of the applied "
+                        "state, and those do not hold the dynamics (a projection error that no step size removes)")
+    if not isinstance(alg, TDVP2):
+        raise TypeError("thermal_greens_function takes alg = TDVP2(...)")
+    _refuse_sharded(psi.engine.ops, "thermal_greens_function")
+    site = psi.n_phys // 2 if site is None else int(site)
+    if not 0 <= site < psi.n_phys:
+        raise ValueError(f"thermal_greens_function: site {site} out of range (the state has {psi.n_phys} physical sites)")
+    times = [float(t) for t in times]
+    bra = psi.engine.copy()
+    work = psi.engine.copy()
+    work.move_centre(2 * site)
+    ket = work.apply_op(2 * site, op)
+    ket.move_centre(0)                  # (its norm now sits beside normalised tensors: the amplitude, applied by `transition`)
+    for eng in (bra, ket):
+        _tdvp_setup(FiniteMPS(eng, psi.L), None, alg)
+    Cm = np.zeros((len(times), psi.n_phys), dtype=np.complex128)
+    tw = np.zeros((len(times), 2))
+    Cm[0] = bra.transition(op, ket)[::2]
+    for k in range(1, len(times)):
+        h = times[k] - times[k - 1]
+        # a state `cool` has never stepped has the beta = 0 tables, dimension 1 between rungs, and so has the state applied to it:
+        # the first interval opens them with the sweeps of SEED_STEPS, as the first step of `cool` does (in real time here, and
+        # counted in that interval)
+        seeds = [min(eps, 0.25 * h) for eps in SEED_STEPS] if k == 1 and not psi.seeded else []
+        for j, eng in enumerate((bra, ket)):
+            k0 = len(eng.stats)
+            for dt in seeds + [h - sum(seeds)]:
+                eng.tdvp_sweep(dt)
+            tw[k, j] = float(sum(s.trunc_weight for s in eng.stats[k0:]))
+        Cm[k] = bra.transition(op, ket)[::2]
+    return {"times": np.array(times), "C": Cm, "trunc_weight": tw, "site": site, "beta": psi.beta, "op": op}
+
+
+def _adjoint_pair(part_op, hole_op):
+    """True if the two operator names are a creator and the annihilator of the same orbital ("c+" / "c", "c+_up" / "c_up", ...)"""
+    alias = _engine.DMRG2.OP_ALIASES
+    p, h = alias.get(part_op, part_op), alias.get(hole_op, hole_op)
+    return p.startswith("cdag") and h == "c" + p[len("cdag"):]
+
+
+def thermal_spectral_function(part, hole, q, omegas, eta):
+    """A(q, omega) = -Im G^R(q, omega) / pi at finite temperature from two thermal_greens_function results of the same state, times
+    and site: `part` for a creator (op = "c+") and `hole` for its annihilator (op = "c"), combined into the retarded function
+    G^R(x, t) = -i theta(t) (C_part(t, x) + conj(C_hole(t, x))) = -i theta(t) Tr[rho_beta {c_x(t), c+_site}] and transformed by
+    spectral_function: its Gaussian window of width eta, its trapezoidal rule over the times, its Fourier transform in x - site;
+    q and omegas scalars or arrays -> [len(q), len(omegas)].  Host only.  Conventions: the anticommutator sums over the components
+    of the operator's multiplet, so in the SU(2) modes A is the sum of both spins and integrates to 2 over omega at q = 0 (to 1 for
+    "c+_up" / "c_up" in the spinful mode); omega is measured from the chemical potential, since K = H - mu N drives the dynamics;
+    as for spectral_function, an open chain has no momentum eigenstates and q is the variable conjugate to the distance from
+    `site`.  Results that do not belong together raise ValueError."""
+    for key in ("site", "beta", "times", "C", "op"):
+        if key not in part or key not in hole:
+            raise ValueError(f"thermal_spectral_function takes two thermal_greens_function results ('{key}' is missing)")
+    tp, th = np.asarray(part["times"], dtype=float), np.asarray(hole["times"], dtype=float)
+    if part["site"] != hole["site"] or part["beta"] != hole["beta"]:
+        raise ValueError("thermal_spectral_function: the particle and the hole part differ in site or beta")
+    if tp.shape != th.shape or not np.array_equal(tp, th) or np.shape(part["C"]) != np.shape(hole["C"]):
+        raise ValueError("thermal_spectral_function: the particle and the hole part differ in their times or their sites")
+    if isinstance(part["op"], str) and isinstance(hole["op"], str) and not _adjoint_pair(part["op"], hole["op"]):
+        raise ValueError(f"thermal_spectral_function: op '{part['op']}' (particle) and '{hole['op']}' (hole) are not a creator and "
+                         "its annihilator")
+    both = dict(part, C=np.asarray(part["C"]) + np.conj(np.asarray(hole["C"])))
+    return spectral_function(both, q, omegas, eta)
 
 
 # ---- energy variance and extrapolation ---------------------------------------------------------------------------------
