@@ -155,6 +155,8 @@ class ThermalMPS(FiniteMPS):
     beta: float = 0.0
     log_z: float = 0.0
     seeded: bool = False        # cool() has put the first bond directions into the beta = 0 tables (SEED_STEPS)
+    simul: object = None        # the model: the mirror scheme builds its generator from it
+    mirror: object = None       # engine.CMpo of models.purified_hamiltonian(simul, n_phys, "mirror"), built on first use
 
 
 SEED_STEPS = (1e-10, 1e-5)      # imaginary-time lengths of the two sweeps that open the bond tables of the beta = 0 state
@@ -415,7 +417,7 @@ def thermal_state(simul: Simulation, L: int | None = None, ops=None):
     n_phys = len(H) // 2
     bonds, tensors = mps.infinite_temperature_mps(n_phys, H.sym)
     eng = _engine.DMRG2(ops, H, bonds, tensors)
-    return ThermalMPS(eng, len(H), n_phys, 0.0, n_phys * float(np.log(4.0)))
+    return ThermalMPS(eng, len(H), n_phys, 0.0, n_phys * float(np.log(4.0)), simul=simul)
 
 
 def cool(psi: ThermalMPS, betas, alg, dbeta: float = 0.05, observe=None):
@@ -943,8 +945,17 @@ def spectral_function_cv(res, q):
     return A if np.ndim(q) else A[0]
 
 
-# ---- finite-temperature dynamics: both states of the purification evolved -----------------------------------------------
-def thermal_greens_function(psi, times, alg, op="c+", site=None):
+# ---- finite-temperature dynamics: both states of the purification evolved, or the ket alone under the mirrored generator -----
+def _mirror_mpo(psi):
+    """the MPO of G = K x 1 - 1 x K~ of a ThermalMPS on its context (models.purified_hamiltonian, ancilla="mirror"), built once"""
+    if psi.mirror is None:
+        if psi.simul is None:
+            raise ValueError("this ThermalMPS does not know its model (it was not made by thermal_state): no mirrored generator")
+        psi.mirror = _engine.CMpo(psi.engine.ops, models.purified_hamiltonian(psi.simul, psi.n_phys // psi.simul.bands, "mirror"))
+    return psi.mirror
+
+
+def thermal_greens_function(psi, times, alg, op="c+", site=None, ancilla="idle"):
     """C[t, x] = <psi_beta| exp(+i K t) O+_x exp(-i K t) O_site |psi_beta> = Tr[rho_beta O+_x(t) O_site] of a ThermalMPS at its
     current beta, for all n_phys physical sites x and the increasing list `times` (the first entry is the time of the applied
     state itself, normally 0); site is a physical index, n_phys // 2 by default.  K is the Hamiltonian attached to the state
@@ -958,7 +969,13 @@ def thermal_greens_function(psi, times, alg, op="c+", site=None):
     greens_function removes with exp(+i E0 t): there is none here.  One-site TDVP() is refused.  psi itself is not touched.
     -> {"times", "C": [len(times), n_phys] complex, "trunc_weight": [len(times), 2] (discarded weight of the step that led to each
     time, bra and ket), "site", "beta", "op"}; spectral_function takes the result as it is, thermal_spectral_function a particle
-    and a hole result.  The factor -i and the step function are left to the caller, as for greens_function."""
+    and a hole result.  The factor -i and the step function are left to the caller, as for greens_function.
+    ancilla="mirror" (DESIGN 4i): the ancillas are evolved backwards with the mirrored Hamiltonian, the generator is G = K x 1 -
+    1 x K~ (models.purified_hamiltonian(..., "mirror")): K~ acts on the ancillas alone, so it commutes with every physical
+    operator, and G annihilates psi_beta.  The bra is psi itself, read only and never evolved; per interval one tdvp_sweep of the ket under G and
+    one `transition` pass.  No phase is owed: the eigenvalue of psi_beta under G is 0.  That holds as well as `cool` made
+    psi_beta (purification_defect measures it).  The result has the same keys, "ancilla" in both schemes; the bra column of
+    "trunc_weight" is all zeros.  A state that was never cooled gets the seed sweeps on the ket, under G."""
     if isinstance(psi, InfiniteMPS):
         raise NotImplementedError("thermal_greens_function needs a chain length: thermal states live on a finite chain, not on an "
                                   "InfiniteMPS")
@@ -970,18 +987,24 @@ def thermal_greens_function(psi, times, alg, op="c+", site=None):
                         "state, and those do not hold the dynamics (a projection error that no step size removes)")
     if not isinstance(alg, TDVP2):
         raise TypeError("thermal_greens_function takes alg = TDVP2(...)")
+    if ancilla not in ("idle", "mirror"):
+        raise ValueError(f"thermal_greens_function: ancilla must be 'idle' or 'mirror', not {ancilla!r}")
     _refuse_sharded(psi.engine.ops, "thermal_greens_function")
     site = psi.n_phys // 2 if site is None else int(site)
     if not 0 <= site < psi.n_phys:
         raise ValueError(f"thermal_greens_function: site {site} out of range (the state has {psi.n_phys} physical sites)")
     times = [float(t) for t in times]
-    bra = psi.engine.copy()
+    mirror = ancilla == "mirror"
+    bra = psi.engine if mirror else psi.engine.copy()      # (mirror: read only -- `transition` does not modify its bra)
     work = psi.engine.copy()
     work.move_centre(2 * site)
     ket = work.apply_op(2 * site, op)
     ket.move_centre(0)                  # (its norm now sits beside normalised tensors: the amplitude, applied by `transition`)
-    for eng in (bra, ket):
+    evolved = (ket,) if mirror else (bra, ket)
+    for eng in evolved:
         _tdvp_setup(FiniteMPS(eng, psi.L), None, alg)
+    if mirror:
+        ket.set_mpo(_mirror_mpo(psi))
     Cm = np.zeros((len(times), psi.n_phys), dtype=np.complex128)
     tw = np.zeros((len(times), 2))
     Cm[0] = bra.transition(op, ket)[::2]
@@ -991,13 +1014,29 @@ def thermal_greens_function(psi, times, alg, op="c+", site=None):
         # the first interval opens them with the sweeps of SEED_STEPS, as the first step of `cool` does (in real time here, and
         # counted in that interval)
         seeds = [min(eps, 0.25 * h) for eps in SEED_STEPS] if k == 1 and not psi.seeded else []
-        for j, eng in enumerate((bra, ket)):
+        for j, eng in enumerate(evolved, start=2 - len(evolved)):
             k0 = len(eng.stats)
             for dt in seeds + [h - sum(seeds)]:
                 eng.tdvp_sweep(dt)
             tw[k, j] = float(sum(s.trunc_weight for s in eng.stats[k0:]))
         Cm[k] = bra.transition(op, ket)[::2]
-    return {"times": np.array(times), "C": Cm, "trunc_weight": tw, "site": site, "beta": psi.beta, "op": op}
+    return {"times": np.array(times), "C": Cm, "trunc_weight": tw, "site": site, "beta": psi.beta, "op": op, "ancilla": ancilla}
+
+
+def purification_defect(psi):
+    """two-site variance of the mirrored generator G = K x 1 - 1 x K~ on a ThermalMPS -> the result type of
+    energy_variance: .total, .site [L], .bond [L - 1] over the 2 n_phys chain sites, .energy = <psi|G|psi>.  G annihilates the exact
+    psi_beta, so this is 0 for it and measures what truncation and the step error of `cool` left: the quality figure of a cooled
+    state for thermal_greens_function(..., ancilla="mirror"), whose bra is taken to be stationary.  On the interleaved chain every
+    pair term of G spans at least one site in between (range >= 2), so the figure is a lower bound of <G^2> - <G>^2, as
+    energy_variance is for longer-range Hamiltonians.  Measured on a copy with G attached (engine.DMRG2.variance); psi is not
+    touched."""
+    if not isinstance(psi, ThermalMPS):
+        raise TypeError("purification_defect takes the ThermalMPS of thermal_state / cool")
+    _refuse_sharded(psi.engine.ops, "purification_defect")
+    work = psi.engine.copy()
+    work.set_mpo(_mirror_mpo(psi))
+    return work.variance()
 
 
 def _adjoint_pair(part_op, hole_op):

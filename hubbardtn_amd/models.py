@@ -16,7 +16,7 @@ matching the 1 / sqrt(2) entries of src:284-290):
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from math import sqrt
+from math import factorial, sqrt
 
 import numpy as np
 
@@ -757,15 +757,231 @@ def hamiltonian(sim: Simulation, L: int):
     return _build_mpo(nsites, onsite, pairs, symmetry_of(sim), strings=strings)
 
 
-def purified_hamiltonian(sim: Simulation, L: int):
-    """H' of the purified (ancilla-doubled) chain of a thermal state: the model's terms on the physical sublattice of a chain
-    of twice as many sites -- physical site s at 2 s, its ancilla at 2 s + 1, nothing on the ancillas.  The Jordan-Wigner
-    pass operators of the hopping channels run across the ancillas like across any site in between; every ancilla parity
-    commutes with H', and a gauge that is diagonal in the occupation basis removes the signs they leave.  Models
-    with `U112` / `U1111` strings are refused: a string is a product over a contiguous range of sites."""
+# ---- rung conjugation: the ancilla image of a physical operator on the beta = 0 rung ----------------------------------------
+def _cg(j1, m1, j2, m2, j, m):
+    """Clebsch-Gordan coefficient <j1 m1; j2 m2 | j m>, all arguments doubled (Racah's formula, Condon-Shortley phases)"""
+    if m1 + m2 != m or not abs(j1 - j2) <= j <= j1 + j2 or (j1 + j2 + j) % 2 or abs(m1) > j1 or abs(m2) > j2 or abs(m) > j:
+        return 0.0
+    f = lambda n2: float(factorial(n2 // 2))
+    pref = (j + 1) * f(j + j1 - j2) * f(j - j1 + j2) * f(j1 + j2 - j) / f(j1 + j2 + j + 2)
+    pref *= f(j + m) * f(j - m) * f(j1 - m1) * f(j1 + m1) * f(j2 - m2) * f(j2 + m2)
+    acc = 0.0
+    for k in range(max(0, (j2 - j - m1) // 2, (j1 + m2 - j) // 2), min((j1 + j2 - j) // 2, (j1 - m1) // 2, (j2 + m2) // 2) + 1):
+        acc += (-1) ** k / (f(2 * k) * f(j1 + j2 - j - 2 * k) * f(j1 - m1 - 2 * k) * f(j2 + m2 - 2 * k) * f(j - j2 + m1 + 2 * k)
+                            * f(j - j1 - m2 + 2 * k))
+    return sqrt(pref) * acc
+
+
+def _site_offsets(sym):
+    """first index of every site multiplet in the dense site basis (component m = j, j - 2, ... within a multiplet)"""
+    off = [0]
+    for (_, j) in sym.site_mult:
+        off.append(off[-1] + (j + 1 if sym.su2 else 1))
+    return off
+
+
+def _dense_components(sym, op):
+    """(k, dN, red) -> the dense matrices of the operator's components q = k, k - 2, ..., -k (one matrix in the abelian kind):
+    <s' m'| O_q |s m> = red[s', s] <j_s m; k q | j_s' m'>"""
+    k, _, red = op
+    if not sym.su2:
+        return [np.array(red, dtype=float)]
+    off = _site_offsets(sym)
+    comps = [np.zeros((off[-1], off[-1])) for _ in range(k + 1)]
+    for so, (_, jo) in enumerate(sym.site_mult):
+        for si, (_, ji) in enumerate(sym.site_mult):
+            if red[so, si] == 0.0:
+                continue
+            for q in range(k + 1):
+                for mo in range(jo + 1):
+                    for mi in range(ji + 1):
+                        comps[q][off[so] + mo, off[si] + mi] += red[so, si] * _cg(ji, ji - 2 * mi, k, k - 2 * q, jo, jo - 2 * mo)
+    return comps
+
+
+def _reduce_components(sym, comps, k):
+    """inverse of _dense_components; raises if the matrices are not the components of one tensor operator of rank k"""
+    if not sym.su2:
+        return np.array(comps[0], dtype=float)
+    off, ns = _site_offsets(sym), sym.n_site
+    red = np.zeros((ns, ns))
+    for so, (_, jo) in enumerate(sym.site_mult):
+        for si, (_, ji) in enumerate(sym.site_mult):
+            cg = np.array([[[_cg(ji, ji - 2 * mi, k, k - 2 * q, jo, jo - 2 * mo) for mi in range(ji + 1)] for mo in range(jo + 1)]
+                           for q in range(k + 1)])
+            blk = np.array([c[off[so]:off[so + 1], off[si]:off[si + 1]] for c in comps])
+            r = float(np.sum(blk * cg) / np.sum(cg * cg)) if cg.any() else 0.0
+            if np.abs(blk - r * cg).max() > 1e-13:
+                raise ValueError(f"rung conjugate: not a tensor operator of rank {k}/2")
+            red[so, si] = r
+    return red
+
+
+def rung_matrix(sym):
+    """R[a, b]: the amplitudes of the beta = 0 rung mps.infinite_temperature_mps builds, |rung> = sum_ab R[a, b] |a>_phys |b>_anc,
+    in the dense site basis (|0>, |up>, |dn>, |up dn>), expanded from its two site tensors with their structure tensors
+    (right-type: CG(j_l j_s | j_r) sqrt((j_l + 1) / (j_r + 1)) in the SU(2) kinds, 1 in the abelian kind)"""
+    from .mps import infinite_temperature_mps
+    _, (P, A) = infinite_temperature_mps(1, sym)
+    off = _site_offsets(sym)
+    R = np.zeros((off[-1], off[-1]))
+    for (l, s, c), p in P.items():
+        for (c2, t, r), a in A.items():
+            if c2 != c:
+                continue
+            amp = float((np.asarray(p) @ np.asarray(a))[0, 0])
+            if not sym.su2:
+                R[off[s], off[t]] += amp
+                continue
+            js, jt, jc = sym.site_mult[s][1], sym.site_mult[t][1], c[1]
+            for ms in range(js + 1):
+                for mt in range(jt + 1):
+                    # left sector spin 0, right sector spin 0: the bond in between carries m_c = m_s
+                    w = _cg(0, 0, js, js - 2 * ms, jc, js - 2 * ms) * sqrt(1.0 / (jc + 1))
+                    w *= _cg(jc, js - 2 * ms, jt, jt - 2 * mt, 0, 0) * sqrt(jc + 1.0)
+                    R[off[s] + ms, off[t] + mt] += amp * w
+    return R
+
+
+def _op_tuple(sym, op):
+    return sym.site_ops[op] if isinstance(op, str) else op
+
+
+def _rung_conjugate(sym, op):
+    """(k, dN, matrix) of O~ with (O x 1)|rung> = (1 x O~)|rung> as plain tensor products: component by component
+    O R = R O~^T, so O~ = (R^-1 O R)^T, then back to reduced form.  O~ carries the charge and rank of O, and
+    (A B)~ = B~ A~."""
+    k, dN, _ = op = _op_tuple(sym, op)
+    R = rung_matrix(sym)
+    Rinv = np.linalg.inv(R)
+    return (k, dN, _reduce_components(sym, [(Rinv @ c @ R).T for c in _dense_components(sym, op)], k))
+
+
+def rung_conjugate_su2u1(op):
+    """SU(2) x U(1): the rung is 1/2 (|0>|2> + |2>|0> + |up>|dn> - |dn>|up>), a spin singlet of charge 2"""
+    return _rung_conjugate(SU2U1, op)
+
+
+def rung_conjugate_u1u1(op):
+    """U(1) x U(1): the rung is 1/2 (|0>|2> + |2>|0> + |up>|dn> + |dn>|up>), all signs +"""
+    return _rung_conjugate(U1U1, op)
+
+
+def rung_conjugate_su2p(op):
+    """SU(2) with parity: the rung of the SU(2) x U(1) kind; |0>|2> and |2>|0> share the sector (0, 0) as two multiplets"""
+    return _rung_conjugate(SU2P, op)
+
+
+def rung_conjugate(sym, op):
+    """the ancilla operator O~ of a site operator O (a name of sym.site_ops or a (k, dN, matrix) tuple) -> (k, dN, matrix)"""
+    return (rung_conjugate_su2u1, rung_conjugate_u1u1, rung_conjugate_su2p)[sym.kind](_op_tuple(sym, op))
+
+
+def _times(sym, a, b):
+    """the product A B of two site operators one of which is a scalar that is diagonal in the site basis (F, id)"""
+    a, b = _op_tuple(sym, a), _op_tuple(sym, b)
+    if not sym.su2:
+        return (a[0] + b[0], a[1] + b[1], a[2] @ b[2])
+    if a[0] == 0 and a[1] == 0:
+        return (b[0], b[1], np.diag(a[2])[:, None] * b[2])
+    return (a[0], a[1], a[2] * np.diag(b[2])[None, :])
+
+
+def _named(sym, op):
+    """a site operator as a combination of named ones of its charge and rank, [(name, coefficient)]: the on-site operators
+    of the models first, then the operators of the symmetry's term channels.  The MPO of the mirrored ancilla terms is written
+    in these names alone, so everything that reads an MPO by name reads it as well."""
+    k, dN, m = op
+    names = [n for n in ("id", "n", "docc", "sz") if n in sym.site_ops]
+    for chans in sym.channels.values():
+        for (_, _, op_open, _, op_close, _) in chans:
+            names += [n for n in (op_open, op_close) if n not in names]
+    basis = []
+    for n in names:
+        kk, dd, mm = sym.site_ops[n]
+        if (kk, dd) == (k, dN) and np.linalg.matrix_rank(np.array([b.ravel() for _, b in basis] + [mm.ravel()])) > len(basis):
+            basis.append((n, mm))
+    if not m.any():
+        return []
+    if not basis:
+        raise ValueError("rung conjugate: no named site operator of this charge")
+    x, *_ = np.linalg.lstsq(np.array([b.ravel() for _, b in basis]).T, m.ravel(), rcond=None)
+    if np.abs(sum(c * b for c, (_, b) in zip(x, basis)) - m).max() > 1e-13:
+        raise ValueError("rung conjugate: the operator is no combination of the named site operators")
+    # (the coefficients carry the rounding of the Clebsch-Gordan square roots, a few 1e-16: taken off at 1e-13, the bound just checked)
+    return [(n, float(round(c, 13))) for c, (n, _) in zip(x, basis) if abs(c) > 1e-13]
+
+
+def _mirror_terms(sym, onsite, pairs):
+    """the terms of -K~ on the ancilla sublattice (site s -> 2 s + 1) for the terms of K on the physical one ->
+    (symmetry with the ancilla channels added, onsite, pairs).
+    On-site term c O_s: -c O~ on the ancilla.  Even pair term c A_i B_j: -c A~ B~, the pass operator the identity.  Odd pair
+    term: as fermionic operators c A^_i B^_j, with the channel's plain factors open = A F, pass F, close = B.  On |I> every rung
+    to the left is even, so X^_s |I> = X^c_s |I> with X^c the fermionic ancilla operator of local matrix X~ F (its string
+    crosses the physical site of its own rung, and F~ = F).  Then A^_i B^_j |I> = A^_i B^c_j |I> = -B^c_j A^c_i |I> =
+    +A^c_i B^c_j |I>: reversed order, and the two odd factors anticommute back.  As plain factors on the chain:
+    open' = A~ = F (open)~, pass F across physical and ancilla sites alike, close' = (close)~ F.  Operators that come out
+    as the identity on one site (n~ = 2 - n) turn the pair term into an on-site one."""
+    chans = dict(sym.channels)
+    anc_onsite, anc_pairs = {}, []
+    for s, terms in onsite.items():
+        for (op, coef) in terms:
+            for (name, c) in _named(sym, rung_conjugate(sym, op)):
+                anc_onsite.setdefault(2 * s + 1, []).append((name, -coef * c))
+    done = {}
+    for (i, j, kind, coef) in pairs:
+        if kind not in sym.channels:
+            raise NotImplementedError(f"term kind '{kind}' is not available in the {sym.name} mode (SURVEY 8f.2)")
+        if kind not in done:
+            new, local = [], []                     # local: (site 0 = i / 1 = j, name, factor) of products with an identity in them
+            for (sub, q, op_open, op_pass, op_close, fac) in sym.channels[kind]:
+                co, cc = rung_conjugate(sym, op_open), rung_conjugate(sym, op_close)
+                if op_pass == "F":
+                    co, cc = _times(sym, "F", co), _times(sym, cc, "F")
+                elif op_pass != "id":
+                    raise NotImplementedError(f"mirrored terms: pass operator '{op_pass}'")
+                for (a, ca) in _named(sym, co):
+                    for (b, cb) in _named(sym, cc):
+                        if "id" in (a, b):
+                            if op_pass != "id" or q != (0, 0):
+                                raise ValueError("mirrored terms: an identity factor in a charged channel")
+                            local.append((0, a, fac * ca * cb) if b == "id" else (1, b, fac * ca * cb))
+                        else:
+                            new.append((f"~{sub}:{a}:{b}", q, a, op_pass, b, fac * ca * cb))
+            chans["~" + kind], done[kind] = tuple(new), local
+        anc_pairs.append((2 * i + 1, 2 * j + 1, "~" + kind, -coef))
+        for (which, name, f) in done[kind]:
+            anc_onsite.setdefault(2 * (j if which else i) + 1, []).append((name, -coef * f))
+    merged = {}
+    for s, terms in anc_onsite.items():             # one entry per operator and site
+        acc = {}
+        for (name, c) in terms:
+            acc[name] = acc.get(name, 0.0) + c
+        merged[s] = [(name, c) for name, c in acc.items() if c != 0.0]
+    return Symmetry(sym.kind, sym.name, sym.site_mult, sym.site_ops, chans, sym.site_electrons), merged, anc_pairs
+
+
+def purified_hamiltonian(sim: Simulation, L: int, ancilla: str = "idle"):
+    """The generator of the purified (ancilla-doubled) chain of a thermal state, physical site s at 2 s, its ancilla at 2 s + 1.
+    ancilla="idle": H' = K x 1, the model's terms on the physical sublattice of a chain of twice as many sites, nothing on the
+    ancillas.  The Jordan-Wigner pass operators of the hopping channels run across the ancillas like across any site in
+    between; every ancilla parity commutes with H', and a gauge that is diagonal in the occupation basis removes the signs
+    they leave.
+    ancilla="mirror": G = K x 1 - 1 x K~, K~ the image of K on the ancilla sublattice under the rung conjugation of the beta = 0
+    state (rung_conjugate, _mirror_terms): (K x 1)|I> = (1 x K~)|I> and the two commute, so G exp(-beta K / 2)|I> = 0
+    for every beta -- the thermal state is stationary under G, and only the ket of a thermal Green's function needs evolving.
+    Models with `U112` / `U1111` strings are refused: a string is a product over a contiguous range of sites."""
+    if ancilla not in ("idle", "mirror"):
+        raise ValueError(f"purified_hamiltonian: ancilla must be 'idle' or 'mirror', not {ancilla!r}")
     nsites, onsite, pairs, strings = model_terms(sim, L)
     if strings:
         raise NotImplementedError("purified_hamiltonian: the U112 / U1111 operator strings of MB_Sim cover contiguous sites and "
                                   "have no form with ancillas in between")
-    return _build_mpo(2 * nsites, {2 * s: list(v) for s, v in onsite.items()},
-                      [(2 * i, 2 * j, kind, coef) for (i, j, kind, coef) in pairs], symmetry_of(sim))
+    sym = symmetry_of(sim)
+    onsite2 = {2 * s: list(v) for s, v in onsite.items()}
+    pairs2 = [(2 * i, 2 * j, kind, coef) for (i, j, kind, coef) in pairs]
+    if ancilla == "idle":
+        return _build_mpo(2 * nsites, onsite2, pairs2, sym)
+    sym_anc, anc_onsite, anc_pairs = _mirror_terms(sym, onsite, pairs)
+    onsite2.update(anc_onsite)
+    return MPO(list(_build_mpo(2 * nsites, onsite2, pairs2 + anc_pairs, sym_anc)), sym)     # (the names are the symmetry's own)
