@@ -52,6 +52,16 @@ NULLPROJ_DT = np.dtype([("r_off", "<i8"), ("q_off", "<i8"), ("m", "<i4"), ("n", 
 assert NULLPROJ_DT.itemsize == 64
 
 
+SAMPLE_DT = np.dtype([("rho_off", "<i8"), ("a_off", "<i8"), ("t_off", "<i8"), ("out_off", "<i8"), ("n_l", "<i4"), ("n_r", "<i4"),
+                      ("lda", "<i4"), ("s", "<i4"), ("probe_unit0", "<i4"), ("close_unit0", "<i4"), ("coef", "<f8")], align=False)  # htn_sample_item
+assert SAMPLE_DT.itemsize == 64
+
+
+def sample_units(m, n):
+    """HTN_SAMPLE_UNITS"""
+    return 0 if m <= 0 or n <= 0 else ((m + 63) // 64) * ((n + 15) // 16)
+
+
 def nullproj_units(m, n, side):
     """HTN_NULLPROJ_UNITS"""
     return 0 if m <= 0 or n <= 0 else ((m if side else n) + 15) // 16
@@ -135,7 +145,7 @@ assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(Idmr
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
            "htn_dots_scratch_elems", "htn_dots_z", "htn_axpys_z", "htn_scale_inv_sqrt_z",
            "htn_jacobi_svd_z", "htn_batched_copy_z", "htn_lanczos_scratch_elems", "htn_lanczos_z", "htn_lanczos_orth_z",
-           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z", "htn_block_place_z", "htn_krylov_combine2_z"]
+           "htn_trdots_scratch_elems", "htn_block_trdots_z", "htn_krylov_combine_z", "htn_block_place_z", "htn_krylov_combine2_z", "htn_sample_step_z"]
 # entry points shared by libhubbardtn_hip.so and the CPU baseline library (oracle/cpu_backend)
 ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_ctx_set_timing", "htn_comm_unique_id",
                   "htn_ctx_set_comm", "htn_ctx_set_exchange", "htn_mpo_create", "htn_mpo_destroy", "htn_mps_create",
@@ -150,7 +160,7 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo",
                   "htn_mps_apply_op", "htn_mps_transition", "htn_block_nullproj_z", "htn_mps_variance",
                   "htn_site_evolve_move", "htn_tdvp1_sweep", "htn_mps_bond_size", "htn_heff0_apply",
-                  "htn_krylov_solve_z", "htn_bond_solve", "htn_cv_sweep"]
+                  "htn_krylov_solve_z", "htn_bond_solve", "htn_cv_sweep", "htn_mps_sample"]
 
 
 class GemmLaunch(C.Structure):
@@ -206,6 +216,7 @@ def load_library(path: str | None = None):
     lib.htn_krylov_combine_z.argtypes = [vp, i64, i32, vp, i64, vp]
     lib.htn_block_place_z.argtypes = [vp, vp, vp, i32, vp]
     lib.htn_krylov_combine2_z.argtypes = [vp, i64, i32, vp, vp, vp, i32, i64, vp]
+    lib.htn_sample_step_z.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, vp, i32, vp, vp, vp, vp]
     declare_engine(lib)
     for name in EXPORTS + ENGINE_EXPORTS:
         getattr(lib, name)          # raises AttributeError if a declared symbol is missing
@@ -297,6 +308,7 @@ def declare_engine(lib):
                                        EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i32), C.POINTER(f64), vp]
     lib.htn_bond_solve.argtypes = [vp, i32, i32, i32, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
     lib.htn_cv_sweep.argtypes = [vp, f64, f64, C.POINTER(SweepOpts), vp, C.POINTER(f64), C.POINTER(f64)]
+    lib.htn_mps_sample.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
     for name in ENGINE_EXPORTS:
         getattr(lib, name)
 

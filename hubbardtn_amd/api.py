@@ -785,6 +785,69 @@ def momentum_distribution(psi, q):
     return np.real(structure_factor(psi, "hop", q, connected=False)) / 2.0
 
 
+# ---- perfect sampling: occupation snapshots, full counting statistics ---------------------------------------------------
+class Samples:
+    """result of sample: .multiplets int32[n, L] (indices into the symmetry's site multiplets: empty / singly / doubly occupied in
+    the SU(2) kinds, empty / up / dn / up dn in the spinful kind), .log_prob [n] (logarithm of the exact probability of each drawn
+    configuration), .sites (the chain sites behind the columns); .electrons and .sz are derived from the multiplets"""
+
+    def __init__(self, multiplets, log_prob, sites, sym):
+        self.multiplets, self.log_prob, self.sites, self.sym = multiplets, log_prob, sites, sym
+
+    @property
+    def electrons(self):
+        """n_i of every snapshot: int[n, L]"""
+        return np.asarray(self.sym.site_electrons, dtype=np.int64)[self.multiplets]
+
+    @property
+    def sz(self):
+        """S^z_i of every snapshot (spinful U(1) x U(1) kind only: an SU(2) multiplet leaves the spin of a singly occupied site
+        unmeasured)"""
+        if self.sym.su2:
+            raise ValueError("This system is spin independent.")                # the reference's error text (src:1424)
+        return np.array([0.0, 0.5, -0.5, 0.0])[self.multiplets]
+
+    def __len__(self):
+        return len(self.log_prob)
+
+
+def sample(psi, n_samples, seed=0, batch=None):
+    """n_samples independent snapshots of the site occupations of a finite chain, each drawn with its exact probability
+    <psi|prod_i P_{s_i}|psi> by perfect sampling on the device (engine.DMRG2.sample) -> Samples.  The uniforms are
+    numpy.random.default_rng(seed).random((n_samples, chain sites)), so a seed names its snapshots.  Any diagonal n-point
+    function -- full counting statistics, string correlations, n-point density correlations -- is a mean over the snapshots.
+    psi with its centre on site 0 (as after a sweep) is only read; otherwise a copy() with the centre on site 0 is sampled, for which
+    psi's centre is carried to site 0 and back by exact moves (the same state to rounding).  A ThermalMPS is sampled with its
+    ancillas traced out and reports its physical sites: finite-temperature snapshots."""
+    if isinstance(psi, InfiniteMPS):
+        raise NotImplementedError("sampling needs a chain length: snapshots are drawn on a finite chain "
+                                  "(pass L= / use a FiniteMPS), not on an InfiniteMPS")
+    eng = psi.engine
+    if eng.centre() != 0:
+        c = eng.centre()
+        eng.move_centre(0)              # (copy() goes through the tensors with the centre on site 0; the moves are exact)
+        work = eng.copy()
+        eng.move_centre(c)
+        eng = work
+    u = np.random.default_rng(seed).random((int(n_samples), eng.L))
+    thermal = isinstance(psi, ThermalMPS)
+    measure = (np.arange(eng.L) % 2 == 0) if thermal else None
+    occ, logp = eng.sample(u, measure=measure, batch=batch)
+    sites = np.arange(0, eng.L, 2) if thermal else np.arange(eng.L)
+    return Samples(np.ascontiguousarray(occ[:, sites]), logp, sites, eng.sym)
+
+
+def full_counting_statistics(samples, region):
+    """histogram of the particle number in `region` (indices into the columns of samples) -> (N values 0 .. 2 |region|, their
+    relative frequencies, binomial standard errors sqrt(f (1 - f) / n)).  Host only."""
+    region = np.atleast_1d(np.asarray(region, dtype=np.int64))
+    N = samples.electrons[:, region].sum(axis=1)
+    values = np.arange(2 * len(region) + 1)
+    n = len(N)
+    f = np.bincount(N, minlength=len(values))[:len(values)] / max(n, 1)
+    return values, f, np.sqrt(f * (1.0 - f) / max(n, 1))
+
+
 # ---- local operators on a finite MPS: G(x, t) and spectral functions ------------------------------------------------
 def apply_operator(psi, name, site):
     """a new FiniteMPS holding O_site |psi> for the site operator `name` of the state's symmetry ("c", "c+" = "cdag", "n", "S";

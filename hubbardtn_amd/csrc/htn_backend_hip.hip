@@ -78,6 +78,8 @@ struct HipBackend : htn::Backend {
     int64_t trd_scratch_elems = 0;
     void* np_scratch = nullptr;                   // unit sums of block_nullproj (doubles)
     int64_t np_scratch_elems = 0;
+    void* smp_scratch = nullptr;                  // unit sums and scales of sample_step (doubles)
+    int64_t smp_scratch_elems = 0;
     void* comm = nullptr;
     char* stage = nullptr;                        // pinned host staging ring of upload()
     size_t stage_cap = (size_t)32 << 20, stage_pos = 0;
@@ -96,6 +98,7 @@ struct HipBackend : htn::Backend {
         if (lan_scratch) (void)hipFree(lan_scratch);
         if (trd_scratch) (void)hipFree(trd_scratch);
         if (np_scratch) (void)hipFree(np_scratch);
+        if (smp_scratch) (void)hipFree(smp_scratch);
         if (stage) (void)hipHostFree(stage);
         if (land) (void)hipHostFree(land);
         if (own_stream && st) (void)hipStreamDestroy(st);
@@ -360,6 +363,23 @@ struct HipBackend : htn::Backend {
             if (htn_debug_poison()) HIP_TRY(hipMemsetAsync(np_scratch, 0xFF, sizeof(double) * np_scratch_elems, st));
         }
         return htn_block_nullproj_z(R, Q, items_dev, items_host, n_items, out, n_out, np_scratch, st);
+    }
+    int sample_step(void* rho_next, const void* rho, const void* A, void* T, const htn_sample_item* items_dev, const htn_sample_item* items_host,
+                    int n_items, int n_site, int n_samples, int64_t rho_stride, int64_t rho_next_stride, int64_t t_stride, const double* u,
+                    int measure, int32_t* choice, double* logp) override {
+        if (n_items > 0 && !items_host) return htn::set_error("sample_step: the host copy of the items is required");
+        int64_t units = 0;
+        for (int q = 0; q < n_items; ++q) units += HTN_SAMPLE_UNITS(items_host[q].n_l, items_host[q].n_r);
+        const int64_t need = HTN_SAMPLE_SCRATCH_DOUBLES(units, std::max(n_samples, 0));
+        if (need > smp_scratch_elems) {              // (hipFree waits for the launches that still read the old block)
+            if (smp_scratch) HIP_TRY(hipFree(smp_scratch));
+            smp_scratch = nullptr, smp_scratch_elems = 0;
+            HIP_TRY(hipMalloc(&smp_scratch, sizeof(double) * 2 * need));
+            smp_scratch_elems = 2 * need;
+            if (htn_debug_poison()) HIP_TRY(hipMemsetAsync(smp_scratch, 0xFF, sizeof(double) * smp_scratch_elems, st));
+        }
+        return htn_sample_step_z(rho_next, rho, A, T, items_dev, items_host, n_items, n_site, n_samples, rho_stride, rho_next_stride, t_stride, u,
+                                 measure, choice, logp, smp_scratch, st);
     }
     int batched_copy(void* dst, const void* src, const int32_t* idx, const double* scl, const htn_copy_item* items, int n_items,
                      double gscale) override {

@@ -514,6 +514,101 @@ int Backend::block_nullproj(void* R, const void* Q, const htn_nullproj_item* ite
     return upload(out, res.data(), sizeof(double) * res.size());
 }
 
+// One site of perfect sampling (conventions of htn_sample_step_z): per sample T = rho_l A and Re<A, T> per item, p(s) over the
+// items in list order, the draw, rho' = scale x sum coef A^H T over the runs of items with one out_off
+int Backend::sample_step(void* rho_next, const void* rho, const void* A, void* T, const htn_sample_item* items_dev, const htn_sample_item* items,
+                         int n_items, int n_site, int n_samples, int64_t rho_stride, int64_t rho_next_stride, int64_t t_stride, const double* u,
+                         int measure, int32_t* choice, double* logp) {
+    (void)items_dev, (void)T, (void)t_stride;
+    if (n_samples <= 0) return 0;
+    if (n_items <= 0 || !items) return set_error("sample_step: the host copy of the items is required");
+    if (n_site < 1 || n_site > HTN_MAX_SITE) return set_error("sample_step: %d site multiplets", n_site);
+    int64_t a0 = INT64_MAX, a1 = 0;
+    for (int q = 0; q < n_items; ++q) {
+        const htn_sample_item& it = items[q];
+        if (it.n_l < 1 || it.n_r < 1 || it.lda < it.n_l || it.s < 0 || it.s >= n_site) return set_error("sample_step: item %d is malformed", q);
+        a0 = std::min(a0, it.a_off), a1 = std::max(a1, it.a_off + (int64_t)(it.n_r - 1) * it.lda + it.n_l);
+    }
+    const size_t B = (size_t)n_samples;
+    std::vector<cplx> hr(B * (size_t)rho_stride), hn(B * (size_t)rho_next_stride), ha((size_t)(a1 - a0));
+    std::vector<double> hu(B, 0.0), hl(B);
+    std::vector<int32_t> hc(B);
+    // (the runs need not cover the next rho: what lies between them is read first and written back as it was)
+    if (download(hr.data(), rho, sizeof(cplx) * hr.size()) || download(hn.data(), rho_next, sizeof(cplx) * hn.size()) ||
+        download(ha.data(), (const cplx*)A + a0, sizeof(cplx) * ha.size()) || download(hl.data(), logp, sizeof(double) * B))
+        return 1;
+    if (measure && download(hu.data(), u, sizeof(double) * B)) return 1;
+    std::vector<std::vector<cplx>> Ts((size_t)n_items);
+    for (size_t b = 0; b < B; ++b) {
+        const cplx* R = hr.data() + b * (size_t)rho_stride;
+        cplx* O = hn.data() + b * (size_t)rho_next_stride;
+        double p[HTN_MAX_SITE] = {0.0, 0.0, 0.0, 0.0};
+        for (int q = 0; q < n_items; ++q) {
+            const htn_sample_item& it = items[q];
+            const int64_t nl = it.n_l, nr = it.n_r;
+            const cplx *Rl = R + it.rho_off, *Ab = ha.data() + (it.a_off - a0);
+            std::vector<cplx>& Tq = Ts[(size_t)q];
+            Tq.assign((size_t)(nl * nr), cplx(0.0, 0.0));
+            double dot = 0.0;
+            for (int64_t j = 0; j < nr; ++j) {
+                for (int64_t k = 0; k < nl; ++k) {
+                    const cplx a = Ab[k + j * it.lda];
+                    for (int64_t i = 0; i < nl; ++i) Tq[(size_t)(i + j * nl)] += Rl[i + k * nl] * a;
+                }
+                for (int64_t i = 0; i < nl; ++i) {
+                    const cplx a = Ab[i + j * it.lda], t = Tq[(size_t)(i + j * nl)];
+                    dot += a.real() * t.real() + a.imag() * t.imag();
+                }
+            }
+            p[it.s] += it.coef * dot;
+        }
+        double total = 0.0;
+        for (int s = 0; s < n_site; ++s) total += p[s];
+        int pick = -1;
+        double scale = 1.0 / total;
+        if (measure) {
+            const double target = hu[b] * total;
+            int last = -1;
+            double cum = 0.0;
+            for (int s = 0; s < n_site; ++s) {
+                cum += p[s];
+                if (p[s] > 0.0) {
+                    last = s;
+                    if (pick < 0 && cum >= target) pick = s;
+                }
+            }
+            if (pick < 0) pick = last;
+            if (pick < 0) return set_error("sample_step: sample %d has no weight on this site", (int)b);
+            hl[b] += log(p[pick] / total);
+            scale = 1.0 / p[pick];
+        }
+        hc[b] = pick;
+        for (int q = 0; q < n_items;) {
+            const int64_t nr = items[q].n_r, out_off = items[q].out_off;
+            cplx* Or = O + out_off;
+            for (int64_t e = 0; e < nr * nr; ++e) Or[e] = cplx(0.0, 0.0);
+            int r = q;
+            for (; r < n_items && items[r].out_off == out_off; ++r) {
+                const htn_sample_item& it = items[r];
+                if (measure && it.s != pick) continue;
+                const int64_t nl = it.n_l;
+                const cplx* Ab = ha.data() + (it.a_off - a0);
+                const std::vector<cplx>& Tr = Ts[(size_t)r];
+                for (int64_t j = 0; j < nr; ++j)
+                    for (int64_t i = 0; i < nr; ++i) {
+                        cplx s = 0.0;
+                        for (int64_t k = 0; k < nl; ++k) s += std::conj(Ab[k + i * it.lda]) * Tr[(size_t)(k + j * nl)];
+                        Or[i + j * nr] += it.coef * s;
+                    }
+            }
+            for (int64_t e = 0; e < nr * nr; ++e) Or[e] *= scale;
+            q = r;
+        }
+    }
+    if (upload(rho_next, hn.data(), sizeof(cplx) * hn.size()) || upload(choice, hc.data(), sizeof(int32_t) * B)) return 1;
+    return measure ? upload(logp, hl.data(), sizeof(double) * B) : 0;
+}
+
 // ---- the kernel-level entries that have a host-memory statement: what the CPU baseline library exports ------------------
 extern "C" {
 

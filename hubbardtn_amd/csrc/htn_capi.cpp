@@ -1,6 +1,6 @@
 // The C entry points of the bond-update / sweep level and of the IDMRG2 driver, grouped and ordered as the sections of
 // include/hubbardtn_hip.h.  Argument checks and forwarding; what an entry does lives with the htn_mps members it calls
-// (htn_engine.cpp, htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_idmrg.cpp).  The kernel-level entries that the CPU baseline library
+// (htn_engine.cpp, htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp).  The kernel-level entries that the CPU baseline library
 // exports too (htn_krylov_expm_z, htn_krylov_solve_z, htn_qr_blocks_z, htn_block_nullproj_z) are in htn_backend_host.cpp.  Host C++ (no HIP).
 // NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
 #include "htn_engine.h"
@@ -275,6 +275,12 @@ int htn_mps_variance(htn_mps* mps, double* site_host, double* bond_host, double*
     if (!mps) return set_error("htn_mps_variance: bad arguments");
     if (mps->be->activate()) return 1;
     return mps->variance(site_host, bond_host, energy_host, split_host);
+}
+int htn_mps_sample(htn_mps* mps, int32_t n_samples, const double* u_host, const int32_t* measure_host, int32_t batch, int32_t* out_host,
+                   double* logp_host, double* split_host) {
+    if (!mps || (n_samples > 0 && (!u_host || !out_host || !logp_host))) return set_error("htn_mps_sample: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->sample(n_samples, u_host, measure_host, batch, out_host, logp_host, split_host);
 }
 
 // ---- queries of the state ------------------------------------------------------------------------------------------

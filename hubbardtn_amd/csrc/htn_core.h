@@ -375,6 +375,13 @@ struct Backend {
     // the host, upload -- what the CPU baseline library runs; the HIP backend overrides it with the kernel.
     virtual int block_nullproj(void* R, const void* Q, const htn_nullproj_item* items_dev, const htn_nullproj_item* items_host, int n_items,
                                double* out, int n_out);
+    // One site of perfect sampling for n_samples samples (htn_sample_step_z in the header: the three stages, the rule of the draw,
+    // the order of every sum).  u, choice, logp: device arrays of n_samples entries.  Default (htn_backend_host.cpp): download,
+    // plain loops with the same order of sums over items and the same rule, upload (T is not filled) -- what the CPU baseline
+    // library runs; the HIP backend overrides it with the kernels.
+    virtual int sample_step(void* rho_next, const void* rho, const void* A, void* T, const htn_sample_item* items_dev,
+                            const htn_sample_item* items_host, int n_items, int n_site, int n_samples, int64_t rho_stride,
+                            int64_t rho_next_stride, int64_t t_stride, const double* u, int measure, int32_t* choice, double* logp);
     virtual int jacobi_svd(void* G, void* Vj, double* S, const htn_svd_block* desc_dev, const htn_svd_block* desc_host,
                            int n_blocks, int max_m, int max_sweeps, double tol, int32_t* info_dev,
                            const htn_svd_opts* opts) = 0;

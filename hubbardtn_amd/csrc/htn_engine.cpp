@@ -9,7 +9,7 @@
 // This file is the core of the htn_mps state: the plan cache's users, the environments, the H_eff applies and the two-site
 // update step by step.  The rest of the host core sits in one file per concern and is compiled as part of
 // THIS translation unit (included below): htn_backend_host.cpp (host statements of Backend methods), htn_site.cpp (one-site
-// updates, time evolution), htn_overlap.cpp (overlaps, attached states, correlators), htn_applyop.cpp (local operators applied to a state), htn_variance.cpp (the two-site energy variance), htn_idmrg.cpp (the infinite-chain growth
+// updates, time evolution), htn_overlap.cpp (overlaps, attached states, correlators), htn_applyop.cpp (local operators applied to a state), htn_variance.cpp (the two-site energy variance), htn_sample.cpp (perfect sampling), htn_idmrg.cpp (the infinite-chain growth
 // loop), htn_capi.cpp (the C entry points).  One unit on purpose: a build line names htn_plan.cpp (the planner, which includes
 // its own parts in the same way) and this file, as it always did, and g++ -O3 contracts the same fused multiply-adds in the host arithmetic as before the split -- across separate units
 // the CPU baseline library changes its last bits (profiles/r07_engine_refactor_identity.txt, r09_engine_split_identity.txt).
@@ -667,5 +667,6 @@ int htn_mps::set_mpo(htn_mpo* m) {
 #include "htn_overlap.cpp"
 #include "htn_applyop.cpp"
 #include "htn_variance.cpp"
+#include "htn_sample.cpp"
 #include "htn_idmrg.cpp"
 #include "htn_capi.cpp"

@@ -1,4 +1,4 @@
-// Internal to the sweep engine (htn_engine.cpp and the files around it: htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_idmrg.cpp, htn_capi.cpp):
+// Internal to the sweep engine (htn_engine.cpp and the files around it: htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp, htn_capi.cpp):
 // the handles behind the C ABI, device buffers, the compiled-plan records of the plan cache, and the htn_mps state itself.
 // Those files form ONE translation unit (htn_engine.cpp includes the others): the using-directive below and the shared types in
 // namespace htn never meet another unit's names.  What a single one of those files uses stays in that file.  Host C++ (no HIP): device work goes through htn::Backend.
@@ -369,6 +369,9 @@ struct htn_mps {
     int transition(const htn_site_op* op, const htn_mps* ket, cplx* out_host);             // htn_mps_transition (this = the bra)
     // ---- htn_variance.cpp: the two-site energy variance ----
     int variance(double* site_host, double* bond_host, double* energy_host, double* split_host);      // htn_mps_variance
+    // ---- htn_sample.cpp: perfect sampling of site multiplets ----
+    int sample(int32_t n_samples, const double* u_host, const int32_t* measure_host, int32_t batch, int32_t* out_host, double* logp_host,
+               double* split_host);                                                                   // htn_mps_sample
 };
 
 // ---- pieces of the engine that more than one file uses ------------------------------------------------------------------

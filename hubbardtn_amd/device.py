@@ -367,6 +367,18 @@ class HipOps:
                                                           self._p(out), n_out, self._p(scratch), self._stream()), "htn_block_nullproj_z")
         return out.view(max(n_out, 1), 2)[:n_out]
 
+    def sample_step(self, rho_next, rho, A, T, items, n_site, n_samples, rho_stride, rho_next_stride, t_stride, u, measure, choice, logp):
+        """htn_sample_step_z: one site of perfect sampling for n_samples samples; items: host array of abi.SAMPLE_DT, everything
+        else device tensors (rho_next, T, choice and logp are written through their views)"""
+        items = np.ascontiguousarray(items, dtype=abi.SAMPLE_DT)
+        units = sum(abi.sample_units(int(it["n_l"]), int(it["n_r"])) for it in items)
+        scratch = self.empty_f64((units + 1) * max(n_samples, 1))
+        dev = self.to_device(items) if len(items) else None
+        abi.check(self.lib, self.lib.htn_sample_step_z(self._p(rho_next), self._p(rho), self._p(A), self._p(T), self._p(dev), items.ctypes.data,
+                                                       len(items), n_site, n_samples, rho_stride, rho_next_stride, t_stride, self._p(u),
+                                                       1 if measure else 0, self._p(choice), self._p(logp), self._p(scratch), self._stream()),
+                  "htn_sample_step_z")
+
     def batched_copy(self, dst, src, idx, scl, items_dev, nitems, gscale):
         if nitems == 0:
             return

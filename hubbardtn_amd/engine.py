@@ -838,6 +838,31 @@ class DMRG2:
         bond = bond[:self.L - 1]
         return Variance(float(site.sum() + bond.sum()), site, bond, E.value, tuple(split) if timed else None)
 
+    # ---- perfect sampling of site multiplets (htn_mps_sample) ----------------------------------------------
+    def sample(self, u, measure=None, batch=None, timed=False):
+        """independent configurations of site multiplets drawn from |psi|^2, each with its exact probability (Ferris, Vidal, PRB 85,
+        165146): u[n, L] uniforms in [0, 1) -> (occ int32[n, L], logp[n]).  occ holds indices into the symmetry's site multiplets
+        ({0, 1, 2} = empty, singly, doubly occupied in the SU(2) kinds, {0, up, dn, updn} in the spinful kind), logp the logarithm
+        of the probability of each drawn configuration.  measure: L flags; a site with flag 0 is traced (nothing drawn, -1 in occ).
+        batch: samples that advance through a site together (None: the library's default); results do not depend on it.  The
+        centre must be on site 0 (as after a sweep); the state is only read.  timed=True: also (plan, device) seconds."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.ndim != 2 or u.shape[1] != self.L:
+            raise ValueError(f"sample: u must have shape (n, {self.L})")
+        if u.size and not (u.min() >= 0.0 and u.max() < 1.0):
+            raise ValueError("sample: the uniforms must lie in [0, 1)")
+        n = u.shape[0]
+        m = None
+        if measure is not None:
+            m = np.ascontiguousarray(np.asarray(measure) != 0, dtype=np.int32)
+            if m.shape != (self.L,):
+                raise ValueError(f"sample: measure must have {self.L} flags")
+        occ, logp, split = np.zeros((n, self.L), dtype=np.int32), np.zeros(n), np.zeros(2)
+        self._check(self.lib.htn_mps_sample(self.handle, n, u.ctypes.data, None if m is None else m.ctypes.data,
+                                            0 if batch is None else int(batch), occ.ctypes.data, logp.ctypes.data,
+                                            split.ctypes.data if timed else None), "htn_mps_sample")
+        return (occ, logp, tuple(split)) if timed else (occ, logp)
+
     def site_energies(self):
         """genuine <psi|H|psi> of the state as stored, split per site: e_i = energy of all Hamiltonian terms that END
         on site i (on-site terms of i, and every two-site term whose right-most site is i); sum(e) = <psi|H|psi>.

@@ -399,6 +399,48 @@ int htn_block_nullproj_z(void* R, const void* Q, const htn_nullproj_item* items,
                          int32_t n_items, double* out, int32_t n_out, void* scratch, void* stream);
 
 
+/* One site of perfect sampling (Ferris, Vidal, Phys. Rev. B 85, 165146) for a batch of samples: the step htn_mps_sample takes per
+ * site.  Every sample b carries a bond density matrix: one n_c x n_c column-major block (ld n_c) per sector c
+ * of the site's left bond, sample b at rho + b * rho_stride.  Per item -- one stored sub-block A[(l, s); r] of the site tensor,
+ * an n_l x n_r view (ld lda) inside `A`, shared by all samples -- and sample three launches do
+ *   probe    T = rho_l A                                  (n_l x n_r, ld n_l, at T + b * t_stride + t_off) and, per work unit,
+ *            the partial sum of Re<A, T> = Re sum conj(A[i, j]) T[i, j];
+ *   choose   p(s) = sum over the items with that s, in list order, of coef x (the item's units in unit order), P = sum_s p(s) in
+ *            the order s = 0 .. n_site - 1;  measure != 0: s* = the smallest s with p(s) > 0 whose cumulative sum p(0) + .. + p(s)
+ *            is >= u[b] P (the last s with p(s) > 0 if rounding leaves none), choice[b] = s*, logp[b] += log(p(s*) / P),
+ *            scale = 1 / p(s*);  measure == 0 (the site is traced): choice[b] = -1, logp[b] is left alone, scale = 1 / P;
+ *   close    rho'_r = scale x sum over the run of items with that out_off, in list order, of coef A^H T  (n_r x n_r, ld n_r, at
+ *            rho_next + b * rho_next_stride + out_off), items with s != s* left out when the site is measured.  A run no item of
+ *            which is taken is written as zeros; what no run covers is not written.
+ * Items with the same out_off must follow one another (the first of a run owns its close units).  probe_unit0 / close_unit0 are
+ * the running sums of HTN_SAMPLE_UNITS(n_l, n_r) over the items and of HTN_SAMPLE_UNITS(n_r, n_r) over the first items of the
+ * runs (every later item of a run carries the value of the next run's first item); the entry checks them against items_host.
+ * Work unit = 64 rows x 16 columns of one output block of one sample = one workgroup of four waves, each a 16 x 16 tile on
+ * v_mfma_f64_16x16x4_f64 with operands read through the L2 (the site tensor is shared by the batch); grid = units x samples.
+ * No floating-point atomics, every sum in a fixed order: a sample's result does not depend on the batch it runs in and
+ * repeated calls are bit-identical.  Nothing synchronises with the host; nothing outside the T, rho' views, choice[0 .. n_samples)
+ * and logp[0 .. n_samples) is written.  u, choice, logp: device arrays of n_samples entries; items: device array, items_host
+ * the same array in host memory (it sizes the launches); scratch: HTN_SAMPLE_SCRATCH_DOUBLES doubles; n_site <= HTN_MAX_SITE,
+ * n_samples <= 65535.  HIP library only. */
+#define HTN_SAMPLE_UNITS(m, n) ((m) <= 0 || (n) <= 0 ? 0 : (((m) + 63) / 64) * (((n) + 15) / 16))
+#define HTN_SAMPLE_SCRATCH_DOUBLES(probe_units, n_samples) (((int64_t)(probe_units) + 1) * (int64_t)(n_samples))
+typedef struct {
+    int64_t rho_off;            /* rho_l inside a sample's rho                                         */
+    int64_t a_off;              /* the sub-block inside A                                              */
+    int64_t t_off;              /* T_s of this sub-block inside a sample's T                           */
+    int64_t out_off;            /* rho'_r inside a sample's next rho                                   */
+    int32_t n_l, n_r, lda;
+    int32_t s;                  /* site multiplet of the sub-block, 0 .. n_site - 1                    */
+    int32_t probe_unit0;        /* number of the item's first probe unit                               */
+    int32_t close_unit0;        /* number of the first close unit of the item's run                    */
+    double coef;                /* coefficient of the identity on this sub-block in a left-environment step */
+} htn_sample_item;              /* 64 bytes */
+int htn_sample_step_z(void* rho_next, const void* rho, const void* A, void* T, const htn_sample_item* items,
+                      const htn_sample_item* items_host, int32_t n_items, int32_t n_site, int32_t n_samples,
+                      int64_t rho_stride, int64_t rho_next_stride, int64_t t_stride, const double* u, int32_t measure,
+                      int32_t* choice, double* logp, void* scratch, void* stream);
+
+
 /* =====================================================================================================
  * Bond-update / sweep level (ABI 2): what sits behind
  *     find_groundstate(psi0, H, IDMRG2(; trscheme, tol))          src/HubbardFunctions.jl:1010
@@ -731,6 +773,27 @@ int htn_mps_transition(htn_mps* bra, const htn_site_op* op, const htn_mps* ket, 
  * Refused: a chain with boundary environments (an iDMRG window), a context with a communicator or an exchange hook, a state
  * with attached orthogonal states, a state of norm 0. */
 int htn_mps_variance(htn_mps* mps, double* site_host, double* bond_host, double* energy_host, double* split_host);
+
+/* Perfect sampling of a finite open chain (Ferris, Vidal, Phys. Rev. B 85, 165146): n_samples independent configurations of
+ * site multiplets, each drawn with its exact probability <psi|prod_i P_{s_i}|psi> / <psi|psi>, site by site from the left.
+ * The centre must be on site 0 with every other site right-canonical (the state after every sweep); the state is only read.
+ * Every sample carries a bond density matrix rho (one block per sector, trace 1); per site the batch takes one
+ * Backend::sample_step (htn_sample_step_z above: the rule of the draw, the order of every sum).  In the tilde normalisation the
+ * coefficient of every sub-block is 1 and a level closes against the right-canonical remainder with the identity, weight 1, in
+ * every sector: probabilities are plain sums.
+ *   u_host        n_samples x L uniforms in [0, 1), sample-major: u_host[b * L + i] draws site i of sample b
+ *   measure_host  L flags (NULL: all 1); a site with flag 0 is traced: nothing is drawn there, its output is -1
+ *   batch         samples that advance through a site together (<= 0: the default, 256); results do not depend on it
+ *   out_host      n_samples x L multiplet indices (the site multiplets of the symmetry, in its order), -1 = traced
+ *   logp_host     n_samples logarithms of the probability of the drawn configuration (of its measured sites)
+ *   split_host    NULL or two doubles: host wall seconds of [planning, device passes including the downloads]
+ * Nothing synchronises inside a pass: choices and log-probabilities are downloaded once per batch.  The per-site item lists are
+ * cached under keys of their own (a sweep after the call plans what it plans without one).  A state that carries its norm
+ * beside its tensors (htn_mps_apply_op) is sampled as the normalised state.
+ * Refused: a centre that is not on site 0; a chain with boundary environments (an iDMRG window); a context with a communicator
+ * or an exchange hook; a state with attached orthogonal states; a state of norm 0. */
+int htn_mps_sample(htn_mps* mps, int32_t n_samples, const double* u_host, const int32_t* measure_host, int32_t batch,
+                   int32_t* out_host, double* logp_host, double* split_host);
 
 /* y = H_eff(bond i, i+1) x on host vectors in the library's theta layout (size htn_mps_theta_size); tests and
  * Hermiticity checks.  x and y are complex128 host arrays. */
