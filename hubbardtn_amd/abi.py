@@ -112,6 +112,12 @@ class CorrChannel(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class CorrChannel2(C.Structure):
+    """htn_corr_channel2"""
+    _fields_ = [("open", SiteOp * 2), ("close", SiteOp * 2), ("pass_", SiteOp), ("open_dN", C.c_int32), ("open_k", C.c_int32),
+                ("n_close", C.c_int32), ("pad", C.c_int32)]
+
+
 class SvdOpts(C.Structure):
     """htn_svd_opts"""
     _fields_ = [("split_elems", C.c_int32), ("sweeps_hint", C.c_int32), ("rank_cut", C.c_double),
@@ -140,6 +146,7 @@ class IdmrgStats(C.Structure):
 
 
 assert C.sizeof(SiteOp) == 136 and C.sizeof(TrdotItem) == 64 and C.sizeof(CorrChannel) == 4 * 136 + 8
+assert C.sizeof(CorrChannel2) == 5 * 136 + 16
 assert C.sizeof(SweepOpts) == 64 and C.sizeof(IdmrgOpts) == 96 and C.sizeof(IdmrgStats) == 48
 
 EXPORTS = ["htn_last_error", "htn_abi_version", "htn_device_init", "htn_grouped_gemm_z",
@@ -160,7 +167,7 @@ ENGINE_EXPORTS = ["htn_ctx_create", "htn_ctx_destroy", "htn_ctx_backend", "htn_c
                   "htn_krylov_expm_z", "htn_bond_evolve", "htn_site_evolve", "htn_tdvp2_sweep", "htn_mps_set_mpo",
                   "htn_mps_apply_op", "htn_mps_transition", "htn_block_nullproj_z", "htn_mps_variance",
                   "htn_site_evolve_move", "htn_tdvp1_sweep", "htn_mps_bond_size", "htn_heff0_apply",
-                  "htn_krylov_solve_z", "htn_bond_solve", "htn_cv_sweep", "htn_mps_sample"]
+                  "htn_krylov_solve_z", "htn_bond_solve", "htn_cv_sweep", "htn_mps_sample", "htn_mps_correlator2"]
 
 
 class GemmLaunch(C.Structure):
@@ -288,6 +295,7 @@ def declare_engine(lib):
     lib.htn_heff1_apply.argtypes = [vp, i32, vp, vp]
     lib.htn_qr_blocks_z.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.htn_mps_correlator.argtypes = [vp, C.POINTER(CorrChannel), vp, C.POINTER(f64)]
+    lib.htn_mps_correlator2.argtypes = [vp, C.POINTER(CorrChannel2), vp, C.POINTER(f64)]
     lib.htn_krylov_expm_z.argtypes = [C.POINTER(GemmLaunch), i32, i32, i32, vp, i64, i32, f64, f64, f64, i32, vp, i32,
                                       EXCHANGE_FN, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(i32), C.POINTER(f64),
                                       C.POINTER(f64), vp]

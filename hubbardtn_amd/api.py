@@ -785,6 +785,32 @@ def momentum_distribution(psi, q):
     return np.real(structure_factor(psi, "hop", q, connected=False)) / 2.0
 
 
+def bond_correlation_function(psi, kind, connected=False):
+    """Hermitian (L-1) x (L-1) matrix of correlation functions of nearest-neighbour bond operators of a finite chain, indexed by
+    each bond's left site and measured on the device without moving the state: kind "bond": <B_i B_j> with the bond order
+    B_i = sum_s (c+_{i s} c_{i+1 s} + h.c.), "dimer": <(S_i . S_{i+1}) (S_j . S_{j+1})>, "spair": <Delta+_i Delta_j> with the
+    singlet bond pair Delta_i = (c_{i up} c_{i+1 dn} - c_{i dn} c_{i+1 up}) / sqrt 2 (not in the no-U(1) mode); spinful mode also
+    "bond_up", "bond_dn", "dimer_zz", "dimer_xy".  connected=True ("bond", "dimer" and their components) subtracts <O_i><O_j>."""
+    if isinstance(psi, InfiniteMPS):
+        raise NotImplementedError("correlation functions need a chain length: they are measured on a finite chain "
+                                  "(pass L= / use a FiniteMPS), not on an InfiniteMPS")
+    if isinstance(psi, ThermalMPS):
+        raise NotImplementedError("bond correlators of a ThermalMPS: physical neighbours are two chain sites apart in a purified "
+                                  "state, the bond operators of this entry act on adjacent chain sites")
+    return psi.engine.bond_correlator(kind, connected=connected)
+
+
+def bond_structure_factor(psi, kind, q, connected=True):
+    """S(q) = (1 / (L-1)) sum_ij exp(i q (i - j)) C_ij of bond_correlation_function(psi, kind) over the L - 1 bonds; q scalar or
+    array (radians per site).  connected applies to the kinds that have a connected form (all but "spair")."""
+    Cm = bond_correlation_function(psi, kind, connected=connected and kind != "spair")
+    n = Cm.shape[0]
+    qs = np.atleast_1d(np.asarray(q, dtype=float))
+    ph = np.exp(1j * qs[:, None] * np.arange(n)[None, :])                      # [q, i]
+    S = np.einsum("qi,ij,qj->q", ph, Cm, ph.conj()) / n
+    return S if np.ndim(q) else S[0]
+
+
 # ---- perfect sampling: occupation snapshots, full counting statistics ---------------------------------------------------
 class Samples:
     """result of sample: .multiplets int32[n, L] (indices into the symmetry's site multiplets: empty / singly / doubly occupied in

@@ -261,6 +261,11 @@ int htn_mps_correlator(htn_mps* mps, const htn_corr_channel* ch, void* out_host,
     if (mps->be->activate()) return 1;
     return mps->correlator(*ch, (cplx*)out_host, norm_host);
 }
+int htn_mps_correlator2(htn_mps* mps, const htn_corr_channel2* ch, void* out_host, double* norm_host) {
+    if (!mps || !ch || !out_host) return set_error("htn_mps_correlator2: bad arguments");
+    if (mps->be->activate()) return 1;
+    return mps->correlator2(*ch, (cplx*)out_host, norm_host);
+}
 int htn_mps_apply_op(const htn_mps* src, int32_t site, const htn_site_op* op, htn_mps** out, double* norm2_host) {
     if (!src || !op || !out) return set_error("htn_mps_apply_op: bad arguments");
     if (src->be->activate()) return 1;

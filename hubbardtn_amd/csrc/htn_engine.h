@@ -364,6 +364,7 @@ struct htn_mps {
     int set_orthogonal(const htn_mps* const* others, int n);      // htn_mps_set_orthogonal
     int overlap(const htn_mps* ket, double* out_host);            // htn_mps_overlap
     int correlator(const htn_corr_channel& ch, cplx* out_host, double* norm_host);
+    int correlator2(const htn_corr_channel2& ch, cplx* out_host, double* norm_host);
     // ---- htn_applyop.cpp: a local operator applied to the state, transition amplitudes of all sites ----
     int apply_op(int site, const htn_site_op* op, htn_mps** out, double* norm2_host);      // htn_mps_apply_op (this = the source, only read)
     int transition(const htn_site_op* op, const htn_mps* ket, cplx* out_host);             // htn_mps_transition (this = the bra)

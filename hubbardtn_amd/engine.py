@@ -714,7 +714,7 @@ class DMRG2:
 
     # ---- two-point correlation functions (htn_mps_correlator) ----------------------------------------
     def _site_op(self, name) -> abi.SiteOp:
-        k, dN, red = self.sym.site_ops[name]
+        k, dN, red = self.sym.site_ops[name] if isinstance(name, str) else name      # a name of the symmetry or (k, dN, red)
         op = abi.SiteOp()
         op.k, op.dN = int(k), int(dN)
         r = np.zeros((abi.MAX_SITE, abi.MAX_SITE))
@@ -777,6 +777,77 @@ class DMRG2:
             m = np.real(np.diag(self.correlator_channel(one, "id", one, one)[0]))
             Cm = Cm - np.outer(m, m)
         return Cm
+
+    # ---- correlation functions of nearest-neighbour bond operators (htn_mps_correlator2) -------------------
+    def correlator2_channel(self, ops_open, op_pass, ops_close, open_level):
+        """one channel of two bond operators: C[i, j] = <close1_{j+1} close0_j pass.. open1_{i+1} open0_i> for j >= i + 2, what an
+        MPO path with these entries, coefficient 1 and the level open_level = (dN, k) after the open pair measures; zeros
+        elsewhere; already divided by <psi|psi>.  ops_open: two site operators (names of the symmetry or (k, dN, red) tuples),
+        ops_close: two, or one for the one-site close (products on three adjacent sites at j = i + 2).  One pass on the device, the
+        state is only read (any centre position).  -> (C, <psi|psi>)"""
+        if len(ops_open) != 2 or len(ops_close) not in (1, 2):
+            raise ValueError("correlator2_channel: two open operators and one or two close operators")
+        ch = abi.CorrChannel2()
+        for n, o in enumerate(ops_open):
+            ch.open[n] = self._site_op(o)
+        for n, o in enumerate(ops_close):
+            ch.close[n] = self._site_op(o)
+        ch.pass_ = self._site_op(op_pass)
+        ch.open_dN, ch.open_k, ch.n_close = int(open_level[0]), int(open_level[1]), len(ops_close)
+        out = np.zeros((self.L, self.L), dtype=np.complex128)
+        nrm = C.c_double(0.0)
+        self._check(self.lib.htn_mps_correlator2(self.handle, C.byref(ch), out.ctypes.data, C.byref(nrm)), "htn_mps_correlator2")
+        return out, nrm.value
+
+    def _string_values(self, strings, sites):
+        """sum over operator strings [(coef, [site operators], [(dN, k) of the level after each operator but the last])] on
+        `sites` = 2 or 3 adjacent sites, or on two disjoint bonds (4): ndarray[L, L], entry [i, j] with i the first site and j
+        the first site of the second bond (2: j = i + 1, 3: j = i + 2, 4: all j >= i + 2); one device pass per string"""
+        out = np.zeros((self.L, self.L), dtype=np.complex128)
+        for coef, ops, labels in strings:
+            assert len(ops) == sites
+            if sites == 2:
+                ch = abi.CorrChannel()
+                ch.open, ch.pass_, ch.close = self._site_op(ops[0]), self._site_op("id"), self._site_op(ops[1])
+                M = np.zeros((self.L, self.L), dtype=np.complex128)
+                self._check(self.lib.htn_mps_correlator(self.handle, C.byref(ch), M.ctypes.data, None), "htn_mps_correlator")
+                out += coef * np.diag(np.diag(M, 1), 1)
+            else:
+                M, _ = self.correlator2_channel(ops[:2], "F" if labels[1][0] % 2 else "id", ops[2:], labels[1])
+                out += coef * (np.diag(np.diag(M, 2), 2) if sites == 3 else M)
+        return out
+
+    def bond_correlator(self, kind, connected=False):
+        """Hermitian ndarray[L-1, L-1] of correlation functions of nearest-neighbour bond operators, indexed by each bond's left
+        site: kind "bond": <B_i B_j>, B_i = sum_s (c+_{i s} c_{i+1 s} + h.c.) (bond order); "dimer": <(S_i . S_{i+1})
+        (S_j . S_{j+1})>; "spair": <Delta+_i Delta_j>, Delta_i = (c_{i up} c_{i+1 dn} - c_{i dn} c_{i+1 up}) / sqrt 2 (singlet bond
+        pair; needs a particle number, so not in the no-U(1) mode); in the spinful U(1) x U(1) mode also the single components
+        "bond_up", "bond_dn" (one spin species), "dimer_zz" (Sz Sz bonds) and "dimer_xy" ((S+ S- + S- S+) / 2 bonds).  Disjoint
+        bonds (j >= i + 2) take one htn_mps_correlator2 pass per operator string; bonds that share a site are products on
+        three (j = i + 1) or two (j = i) sites, strings of their own (bondcorr.py).  connected=True ("bond", "dimer" and the
+        components) subtracts <O_i><O_j>."""
+        from . import bondcorr
+        tab = bondcorr.strings(self.sym, kind)                    # raises ValueError for a kind the mode does not define
+        if connected and kind == "spair":
+            raise ValueError("connected=True is defined for 'bond' and 'dimer' (<Delta_i> = 0 in a state of fixed particle number)")
+        if self.L < 2:
+            raise ValueError("bond_correlator: the chain has no bond")
+        upper = np.diag(np.diag(self._string_values(tab[0], 2), 1))                  # sites [i, i + 1] -> bond entry (i, i)
+        if self.L >= 3:
+            upper += np.diag(np.diag(self._string_values(tab[1], 3), 2), 1)          # [i, i + 2] -> (i, i + 1)
+        if self.L >= 4:
+            upper += self._string_values(tab[2], 4)[:-1, :-1]
+        d = np.diag(np.diag(upper))
+        Cm = upper - d + (upper - d).conj().T + d.real
+        if connected:
+            m = self.bond_expectation(kind)
+            Cm = Cm - np.outer(m, m)
+        return Cm
+
+    def bond_expectation(self, kind):
+        """ndarray[L-1]: <O_i> of the Hermitian bond operators of bond_correlator ("bond", "dimer" and their components)"""
+        from . import bondcorr
+        return np.real(np.diag(self._string_values(bondcorr.one_bond(self.sym, kind), 2), 1)).copy()
 
     # ---- local operators applied to the state (htn_mps_apply_op / htn_mps_transition) ------------------
     OP_ALIASES = {"c+": "cdag", "c+_up": "cdag_up", "c+_dn": "cdag_dn"}

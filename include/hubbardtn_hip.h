@@ -728,6 +728,34 @@ typedef struct {
 } htn_corr_channel;                 /* 552 bytes */
 int htn_mps_correlator(htn_mps* mps, const htn_corr_channel* ch, void* out_host, double* norm_host);
 
+/* Correlation functions of two nearest-neighbour BOND operators (four-point functions: bond order, bond pair field, dimer),
+ * measured like htn_mps_correlator.  One call gives one channel for all i, j with j >= i + 2: open[0] acts on site i, open[1] on
+ * site i + 1, `pass` on the sites i + 2 .. j - 1, close[0] on site j and close[1] on site j + 1 (n_close = 2; the bonds (i, i+1)
+ * and (j, j+1) are disjoint).  The value is what an MPO path with these entries, coefficient 1 and the intermediate levels
+ *   (open[0].dN, open[0].k) -> (open_dN, open_k) -> .. -> (-close[1].dN, close[1].k) -> scalar
+ * measures (U1_U1: the k of a level is the sum of the operators' k to its left): open_dN / open_k name the level the open pair
+ * couples to, in the SU(2) kinds one of the ranks |k0 - k1| .. k0 + k1; the level between the close operators is fixed by
+ * close[1].  n_close = 1 is the variant with a one-site close: close[0] on site j takes the level (open_dN, open_k) to the
+ * scalar, close[1] is ignored (it is neither read nor part of the plan-cache key; `pad` likewise) and j runs up to L - 1; it
+ * measures products on three adjacent sites (j = i + 2) among others.
+ * Method: the left probe carries the levels [norm, half, open] (norm -> half by open[0], half -> open by open[1]), the right
+ * probe [norm, halfR, open_j ..] (halfR <- norm by close[1], open_j <- halfR by close[0], open_j <- open_j by `pass`); the
+ * halves meet on bond i + 2 in ONE htn_block_trdots_z launch per bond with the block weight of htn_mps_correlator.  Nothing
+ * synchronises inside the pass, the table is downloaded once, the state is only read (any gauge, any centre position).
+ * out_host: L*L complex128, row-major, entry [i*L + j] for j >= i + 2 (j <= L - 2 with n_close = 2), everything else 0; already
+ * divided by <psi|psi>, which is also returned in norm_host (may be NULL).
+ * Errors: charges of the open pair and of the close operators that do not add up to zero; an (open_dN, open_k) the two open
+ * operators cannot couple to; a `pass` that carries a charge; fewer than 4 sites (3 with n_close = 1); n_close outside 1..2; a
+ * chain with boundary environments (an iDMRG window); a context with a communicator or an exchange hook. */
+typedef struct {
+    htn_site_op open[2];            /* on sites i, i + 1                                                  */
+    htn_site_op close[2];           /* on sites j, j + 1 (n_close = 1: close[0] on site j alone)          */
+    htn_site_op pass;               /* on sites i + 2 .. j - 1                                            */
+    int32_t open_dN, open_k;        /* charge / rank of the level after open[1]: what the pair couples to */
+    int32_t n_close, pad;
+} htn_corr_channel2;                /* 696 bytes */
+int htn_mps_correlator2(htn_mps* mps, const htn_corr_channel2* ch, void* out_host, double* norm_host);
+
 /* A reduced site operator O (rank k, charge dN) applied to site `site` of a finite open chain: *out is a NEW state
  * O_site |src> in the total sector fused with (dN, k), on the same context and MPO; src is only read.  The operator's charge
  * leaves through the right end: bonds right of the site are re-labelled by fusion with (dN, k) (an old sector contributes its
