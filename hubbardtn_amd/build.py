@@ -8,7 +8,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-# htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
+# htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_correlator.cpp, htn_applyop.cpp,
+# htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
 # unit on purpose (bit-identical host arithmetic, see its head).  Do not list those files here: every symbol would be defined twice.
 # htn_plan.cpp does the same with the planner: htn_recouple.cpp, htn_layout.cpp, htn_balance.cpp and the htn_plan_*.cpp files.
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("htn_abi.hip", "htn_gemm.hip", "htn_krylov.hip", "htn_svd.hip", "htn_qr.hip", "htn_measure.hip", "htn_place.hip", "htn_nullproj.hip", "htn_sample.hip",

@@ -1,6 +1,7 @@
 // The C entry points of the bond-update / sweep level and of the IDMRG2 driver, grouped and ordered as the sections of
 // include/hubbardtn_hip.h.  Argument checks and forwarding; what an entry does lives with the htn_mps members it calls
-// (htn_engine.cpp, htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp).  The kernel-level entries that the CPU baseline library
+// (htn_engine.cpp, htn_site.cpp, htn_overlap.cpp, htn_correlator.cpp, htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp,
+// htn_idmrg.cpp).  The kernel-level entries that the CPU baseline library
 // exports too (htn_krylov_expm_z, htn_krylov_solve_z, htn_qr_blocks_z, htn_block_nullproj_z) are in htn_backend_host.cpp.  Host C++ (no HIP).
 // NOT a translation unit of its own: #included by htn_engine.cpp (one unit, see its head); never name it on a build line.
 #include "htn_engine.h"

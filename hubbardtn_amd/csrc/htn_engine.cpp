@@ -9,10 +9,12 @@
 // This file is the core of the htn_mps state: the plan cache's users, the environments, the H_eff applies and the two-site
 // update step by step.  The rest of the host core sits in one file per concern and is compiled as part of
 // THIS translation unit (included below): htn_backend_host.cpp (host statements of Backend methods), htn_site.cpp (one-site
-// updates, time evolution), htn_overlap.cpp (overlaps, attached states, correlators), htn_applyop.cpp (local operators applied to a state), htn_variance.cpp (the two-site energy variance), htn_sample.cpp (perfect sampling), htn_idmrg.cpp (the infinite-chain growth
-// loop), htn_capi.cpp (the C entry points).  One unit on purpose: a build line names htn_plan.cpp (the planner, which includes
-// its own parts in the same way) and this file, as it always did, and g++ -O3 contracts the same fused multiply-adds in the host arithmetic as before the split -- across separate units
-// the CPU baseline library changes its last bits (profiles/r07_engine_refactor_identity.txt, r09_engine_split_identity.txt).
+// updates, time evolution), htn_overlap.cpp (overlaps, attached states), htn_correlator.cpp (correlation functions: one probe
+// pass), htn_applyop.cpp (local operators applied to a state), htn_variance.cpp (the two-site energy variance), htn_sample.cpp
+// (perfect sampling), htn_idmrg.cpp (the infinite-chain growth loop), htn_capi.cpp (the C entry points).  One unit on purpose:
+// a build line names htn_plan.cpp (the planner, which includes its own parts in the same way) and this file, as it always did,
+// and g++ -O3 contracts the same fused multiply-adds in the host arithmetic as before the split -- across separate units the
+// CPU baseline library changes its last bits (profiles/r07_engine_refactor_identity.txt, r09_engine_split_identity.txt).
 // Host C++ (no HIP): device work goes through htn::Backend.
 #include "htn_engine.h"
 #include "htn_backend_host.cpp"
@@ -35,13 +37,18 @@ int htn_mps::env_step(char side, int i) {
         (left ? plan_left_env : plan_right_env)(*mpo, *elay[from], lay, W, *e->lay, p);
         return compile2(e, p);
     });
-    if (!c) return 1;
-    DView z = zalloc(c->zsize, false), out = zalloc(c->lay->size, false);
-    if (!z.base || !out.base) return set_error("device allocation failed (%s environment)", left ? "left" : "right");
-    if (gemm(c->d1, {{left ? BUF_L : BUF_R, ebuf[from].ptr()}, {BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}})) return 1;
-    if (gemm(c->d2, {{BUF_S1, site_buf[i].ptr()}, {BUF_Z, z.ptr()}, {BUF_Y, out.ptr()}})) return 1;
+    if (!c || env_launch(left, *c, ebuf[from].ptr(), site_buf[i].ptr(), &ebuf[to])) return 1;
     elay[to] = c->lay;
-    ebuf[to] = out;
+    return 0;
+}
+// The launch half of an environment step, the Hamiltonian's or a probe's (htn_correlator.cpp): stage 1 takes the environment
+// `in` and the site tensor to z, stage 2 the site tensor and z to the new environment, a fresh pool block
+int htn_mps::env_launch(bool left, const EnvC& c, const cplx* in, const cplx* site, DView* out) {
+    DView z = zalloc(c.zsize, false), o = zalloc(c.lay->size, false);
+    if (!z.base || !o.base) return set_error("device allocation failed (%s environment)", left ? "left" : "right");
+    if (gemm(c.d1, {{left ? BUF_L : BUF_R, in}, {BUF_S1, site}, {BUF_Z, z.ptr()}})) return 1;
+    if (gemm(c.d2, {{BUF_S1, site}, {BUF_Z, z.ptr()}, {BUF_Y, o.ptr()}})) return 1;
+    *out = o;
     return 0;
 }
 
@@ -665,6 +672,7 @@ int htn_mps::set_mpo(htn_mpo* m) {
 // ---- the rest of the engine, one file per concern (see the head of this file) ---------------------------------------------
 #include "htn_site.cpp"
 #include "htn_overlap.cpp"
+#include "htn_correlator.cpp"
 #include "htn_applyop.cpp"
 #include "htn_variance.cpp"
 #include "htn_sample.cpp"

@@ -1,4 +1,5 @@
-// Internal to the sweep engine (htn_engine.cpp and the files around it: htn_site.cpp, htn_overlap.cpp, htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp, htn_capi.cpp):
+// Internal to the sweep engine (htn_engine.cpp and the files around it: htn_site.cpp, htn_overlap.cpp, htn_correlator.cpp,
+// htn_applyop.cpp, htn_variance.cpp, htn_sample.cpp, htn_idmrg.cpp, htn_capi.cpp):
 // the handles behind the C ABI, device buffers, the compiled-plan records of the plan cache, and the htn_mps state itself.
 // Those files form ONE translation unit (htn_engine.cpp includes the others): the using-directive below and the shared types in
 // namespace htn never meet another unit's names.  What a single one of those files uses stays in that file.  Host C++ (no HIP): device work goes through htn::Backend.
@@ -191,6 +192,7 @@ struct BondWork {                  // what flows between the steps of one two-si
 }  // namespace htn
 
 struct SiteWork;                   // one-site updates (htn_site.cpp)
+struct CorrProbe;                  // what the probe pass of one correlator entry differs in (htn_correlator.cpp)
 
 struct htn_mps {
     std::atomic<int> refs{1};      // htn_mps_destroy drops one reference (htn_idmrg_window hands out extra ones)
@@ -313,6 +315,7 @@ struct htn_mps {
     }
     // ---- htn_engine.cpp: environments, H_eff applies, the two-site update ----
     int env_step(char side, int i);
+    int env_launch(bool left, const EnvC& c, const cplx* in, const cplx* site, DView* out);
     int left_env(int i) { return env_step('L', i); }
     int right_env(int i) { return env_step('R', i); }
     // H_eff applies (two-site: make_apply, one-site: make_apply1, zero-site on a bond: make_apply0)
@@ -354,7 +357,7 @@ struct htn_mps {
     int bond0_checks(int b, const char* who) const;
     int evolve_site_move(int i, int direction, cplx dt_fwd, cplx dt_back, const htn_sweep_opts& o, htn_bond_stats* st, double* log_growth);
     int tdvp1_sweep(cplx dt, const htn_sweep_opts& o, htn_bond_stats* st, double* E, double* log_norm);
-    // ---- htn_overlap.cpp: overlap environments, attached states, two-point correlation functions ----
+    // ---- htn_overlap.cpp: overlap environments, attached states ----
     // overlap transfers with `ket` as the ket state (this = bra): in -> out across site i
     int ovl_step(char side, const htn_mps* ket, int i, const OvlLayoutP& inl, const DView& in, OvlLayoutP* outl, DView* out);
     int ovl_boundary(const htn_mps* ket, int b, OvlLayoutP* outl, DView* out);
@@ -363,8 +366,14 @@ struct htn_mps {
     void orth_detach();
     int set_orthogonal(const htn_mps* const* others, int n);      // htn_mps_set_orthogonal
     int overlap(const htn_mps* ket, double* out_host);            // htn_mps_overlap
-    int correlator(const htn_corr_channel& ch, cplx* out_host, double* norm_host);
-    int correlator2(const htn_corr_channel2& ch, cplx* out_host, double* norm_host);
+    // ---- htn_correlator.cpp: correlation functions, one probe pass behind the one-site and the bond-operator entry ----
+    int corr_checks(const char* who, const htn_site_op& pass, const char* ends_note);
+    DView site_as(const SiteLayout& want, int i);
+    int probe_step(char side, const Mpo& pm, const MpoSite& W, const EnvLayoutP& inl, const cplx* in, int i, const std::string& key,
+                   EnvLayoutP* outl, DView* out);
+    int corr_pass(const CorrProbe& p, cplx* out_host, double* norm_host);
+    int correlator(const htn_corr_channel& ch, cplx* out_host, double* norm_host);       // htn_mps_correlator
+    int correlator2(const htn_corr_channel2& ch, cplx* out_host, double* norm_host);     // htn_mps_correlator2
     // ---- htn_applyop.cpp: a local operator applied to the state, transition amplitudes of all sites ----
     int apply_op(int site, const htn_site_op* op, htn_mps** out, double* norm2_host);      // htn_mps_apply_op (this = the source, only read)
     int transition(const htn_site_op* op, const htn_mps* ket, cplx* out_host);             // htn_mps_transition (this = the bra)

@@ -1,6 +1,6 @@
 // Batched block trace-dots (htn_block_trdots_z): out[o] = sum_items w * sum_{r,c} A[r, c] * B[c, r].
 // The contraction that closes a two-point correlation function on a bond: a left environment block [n_bra x n_ket] against a
-// right environment block [n_ket x n_bra] (htn_mps::correlator in htn_overlap.cpp).
+// right environment block [n_ket x n_bra] (htn_mps::corr_pass in htn_correlator.cpp).
 //
 // Memory-bound: every element of both operands is read once, so both must be read along their contiguous (column) direction.
 // An item is cut into 32 x 32 tiles of A.  A workgroup of 256 threads reads the A tile column by column straight into

@@ -807,10 +807,7 @@ class DMRG2:
         for coef, ops, labels in strings:
             assert len(ops) == sites
             if sites == 2:
-                ch = abi.CorrChannel()
-                ch.open, ch.pass_, ch.close = self._site_op(ops[0]), self._site_op("id"), self._site_op(ops[1])
-                M = np.zeros((self.L, self.L), dtype=np.complex128)
-                self._check(self.lib.htn_mps_correlator(self.handle, C.byref(ch), M.ctypes.data, None), "htn_mps_correlator")
+                M, _ = self.correlator_channel(ops[0], "id", ops[1])
                 out += coef * np.diag(np.diag(M, 1), 1)
             else:
                 M, _ = self.correlator2_channel(ops[:2], "F" if labels[1][0] % 2 else "id", ops[2:], labels[1])

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "hubbardtn_amd", "csrc")
-# htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
+# htn_engine.cpp #includes htn_backend_host.cpp, htn_site.cpp, htn_overlap.cpp, htn_correlator.cpp, htn_idmrg.cpp and htn_capi.cpp: ONE translation
 # unit on purpose (bit-identical host arithmetic, see its head).  Do not list those files here: every symbol would be defined twice.
 # htn_plan.cpp does the same with the planner: htn_recouple.cpp, htn_layout.cpp, htn_balance.cpp and the htn_plan_*.cpp files.
 SRCS = [os.path.join(CSRC, "htn_plan.cpp"), os.path.join(CSRC, "htn_engine.cpp"), os.path.join(HERE, "htn_backend_cpu.cpp")]

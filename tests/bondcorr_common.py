@@ -85,6 +85,40 @@ def compare_with_ed(eng, corr, kinds, tol=TOL_ED):
     return devs
 
 
+def check_centre_independence(eng, ref, centres):
+    """with the centre moved to each of `centres` (both passes re-lay site tensors): every kind of `ref` = {kind: result with the
+    centre on site 0} within 1e-12, the centre where it was put, the site tensors unchanged bit for bit"""
+    for centre in centres:
+        eng.move_centre(centre)
+        before = [eng.site_vector(i).copy() for i in range(eng.L)]
+        for k, r in ref.items():
+            d = float(np.abs(eng.bond_correlator(k) - r).max())
+            print("centre", centre, k, d)
+            assert d <= 1e-12, (centre, k, d)
+        assert eng.centre() == centre
+        for i in range(eng.L):
+            assert np.array_equal(eng.site_vector(i), before[i]), i
+
+
+def check_repeated_calls_plan_nothing(eng):
+    """eng: a converged L6 engine, centre on site 0.  The second call of correlator("hop") and of bond_correlator("dimer") finds
+    every plan in the cache (no miss) and returns the same bits.  With the centre on site 3 the passes re-lay site tensors: the
+    two-point pass plans the two re-lay directions (at most 2 misses), the bond pass after it and every repeat plan nothing."""
+    assert eng.centre() == 0
+    calls = (("hop", lambda: eng.correlator("hop")), ("dimer", lambda: eng.bond_correlator("dimer")))
+    for moved, allowed in ((False, (None, None)), (True, (2, 0))):
+        if moved:
+            eng.move_centre(3)
+        for (name, call), limit in zip(calls, allowed):
+            m0 = eng.cache_misses
+            a = call()
+            m1 = eng.cache_misses
+            b = call()
+            print(name, "centre", eng.centre(), "misses of the first call", m1 - m0, "of the repeat", eng.cache_misses - m1)
+            assert limit is None or m1 - m0 <= limit, (name, m1 - m0)
+            assert eng.cache_misses == m1 and np.array_equal(a, b), name
+
+
 # ---- free fermions: Wick's theorem from G = sum_s <c+_is c_js> of a spin-symmetric Slater determinant ------------------------------
 def wick_bond(G):
     """<B_i B_j>: <E_ab E_cd> = G_ab G_cd + 2 g_ad (delta_bc - g_cb), g = G / 2, E_ab = sum_s c+_as c_bs, B_i = E_{i,i+1} + E_{i+1,i}"""

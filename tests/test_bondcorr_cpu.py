@@ -1,5 +1,5 @@
 """Bond-operator correlators (htn_mps_correlator2 / engine.DMRG2.bond_correlator / api.bond_correlation_function) on the CPU
-baseline library: the driver, the probe plans and the block weight are the product's own host code (htn_overlap.cpp,
+baseline library: the driver, the probe plans and the block weight are the product's own host code (htn_correlator.cpp,
 htn_plan.cpp).  References: exact diagonalisation with explicitly built operator strings, Wick's theorem on a free-fermion
 state, structural identities."""
 import ctypes
@@ -124,17 +124,13 @@ def test_centre_independence_read_only_repeatable_and_cache_tags(cpu_ops):
     assert np.array_equal(eng.correlator("hop"), hop_before)      # the probe plans of the two entries do not replace each other
     for k, r in ref.items():
         assert np.array_equal(eng.bond_correlator(k), r), k       # repeated calls: bit-identical
-    for centre in (L // 2, L - 1, 0):
-        eng.move_centre(centre)
-        before = [eng.site_vector(i).copy() for i in range(L)]
-        for k, r in ref.items():
-            d = float(np.abs(eng.bond_correlator(k) - r).max())
-            print("centre", centre, k, d)
-            assert d <= 1e-12, (centre, k, d)
-        assert eng.centre() == centre
-        for i in range(L):
-            assert np.array_equal(eng.site_vector(i), before[i]), i
+    bc.check_centre_independence(eng, ref, (L // 2, L - 1, 0))
     assert np.abs(eng.correlator("hop") - hop_before).max() <= 1e-12
+
+
+@pytest.mark.parametrize("mode", bc.MODES)
+def test_repeated_calls_plan_nothing(cpu_ops, mode):
+    bc.check_repeated_calls_plan_nothing(bc.converged_engine(cpu_ops, "L6", mode))
 
 
 def test_error_paths(cpu_ops):

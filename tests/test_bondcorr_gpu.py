@@ -69,3 +69,14 @@ def test_repeatable_read_only_and_two_point_unchanged(hip_ops):
         assert np.array_equal(eng.site_vector(i), before[i]), i
     assert eng.centre() == eng.L // 2
     assert np.array_equal(eng.correlator("hop"), hop_before)      # the probe plans of the two entries do not replace each other
+
+
+def test_centre_independence_and_site_tensors_unchanged(hip_ops):
+    """L = 6, SU(2): the re-lay path of both passes of htn_mps_correlator2, centre in the middle and on the last site"""
+    eng = bc.converged_engine(hip_ops, "L6", "su2")
+    ref = {k: eng.bond_correlator(k) for k in bc.SU2_KINDS}       # centre on site 0
+    bc.check_centre_independence(eng, ref, (eng.L // 2, eng.L - 1))
+
+
+def test_repeated_calls_plan_nothing(hip_ops):
+    bc.check_repeated_calls_plan_nothing(bc.converged_engine(hip_ops, "L6", "su2"))

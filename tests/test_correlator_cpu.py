@@ -1,5 +1,5 @@
 """Two-point correlation functions (htn_mps_correlator / engine.DMRG2.correlator / api.correlation_function) on the CPU
-baseline library: the driver, the probe plans and the block weight are the product's own host code (htn_overlap.cpp,
+baseline library: the driver, the probe plans and the block weight are the product's own host code (htn_correlator.cpp,
 htn_plan.cpp); only the trace-dot kernel is the host default.  References: exact diagonalisation with the operators applied to
 the ED vector by bit operations, dense ED, exact sum rules."""
 import ctypes

@@ -5,7 +5,8 @@
 
 Runs fixed-seed scenarios on a small chain through the Python face of the C ABI and prints one line per scenario: the first 32 hex
 digits of a sha256 over the sweep energies, the per-update energy / discarded weight / matvec, Jacobi-sweep, chi, multiplet, tile
-and segment counts, every bond's spectrum and every exported site tensor, then the plan cache's (hits, misses).  Two builds of
+and segment counts, every bond's spectrum and every exported site tensor (the correlator scenarios: the output table and the
+norm; SU(2) kind, then the spinful U(1) x U(1) kind), then the plan cache's (hits, misses).  Two builds of
 the library compute the same thing exactly when all lines agree.  Without --lib the library of this tree is used (built if
 needed); with --lib nothing is built.
 """
@@ -22,7 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from hubbardtn_amd import abi, engine, idmrg, models, mps  # noqa: E402
+from hubbardtn_amd import abi, bondcorr, engine, idmrg, models, mps  # noqa: E402
 
 
 class Ops:
@@ -140,11 +141,31 @@ def main():
     d.state(ev)
     report("two TDVP2 steps, dt real then imaginary", d, ev)
 
-    d = Digest()
-    Cm, nrm = ev.correlator_channel("n", "id", "n", "n")
-    d.floats(Cm.reshape(-1))
-    d.floats([nrm])
-    report("one correlator channel (n, id, n)", d, ev)
+    def table(name, eng, result):
+        d = Digest()
+        d.floats(result[0].reshape(-1))
+        d.floats([result[1]])
+        report(name, d, eng)
+
+    table("one correlator channel (n, id, n)", ev, ev.correlator_channel("n", "id", "n", "n"))
+
+    def probes(tag, eng):
+        """the probe passes of both correlator entries: a charged channel with a fermionic pass operator, the same with the
+        centre in the middle (both passes re-lay site tensors), then bond-operator strings with two and with one close operator"""
+        _name, _q, op_open, op_pass, op_close, _f = eng.sym.channels["hop"][0]
+        table(f"{tag}hop channel ({op_open}, {op_pass}, {op_close})", eng, eng.correlator_channel(op_open, op_pass, op_close))
+        eng.move_centre(L // 2)
+        table(f"{tag}the same, centre on site {L // 2}", eng, eng.correlator_channel(op_open, op_pass, op_close))
+        _same, shared, far = bondcorr.strings(eng.sym, "bond")
+        for what, (_coef, ops, labels) in (("four-site bond string, two close ops", far[0]), ("three-site bond string, one close op", shared[0])):
+            table(tag + what, eng, eng.correlator2_channel(ops[:2], "F" if labels[1][0] % 2 else "id", ops[2:], labels[1]))
+
+    probes("", ev)
+    Hs = models.hamiltonian(models.OB_Sim([1.0], [4.0], 0.0, 1, 1, 2.0, 50, spin=True), L)
+    bonds, tens = mps.random_mps(L, target, 6, seed=31, sym=Hs.sym)
+    ab = engine.DMRG2(ops, Hs, bonds, tens, chi_full=64, krylovdim=20)
+    ab.sweep()
+    probes("U(1)xU(1): ", ab)
 
 
 if __name__ == "__main__":
