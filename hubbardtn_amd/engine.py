@@ -47,6 +47,11 @@ def _stats(rec) -> BondStats:
     return BondStats(**{k: (float(rec[k]) if rec.dtype[k].kind == "f" else int(rec[k])) for k in rec.dtype.names})
 
 
+def _side(letter) -> int:
+    """the library's index of an environment side: 'L' -> 0, anything else ('R') -> 1"""
+    return 0 if letter == "L" else 1
+
+
 class CMpo:
     """htn_mpo handle built from a models.MPO (list of MPOSite + symmetry; a plain list means SU(2) x U(1) x fZ2)"""
 
@@ -264,11 +269,21 @@ class DMRG2:
     def bonds(self):
         return [self.bond(b) for b in range(self.L + 1)]
 
+    def _table(self, fn, dtype, *args, missing=None):
+        """rows of one of the library's two-call table readers: fn(handle, *args, None) -> count, the same call with a buffer
+        fills it.  missing: the text of the HtnError a negative count raises (without it the count is used as it comes)"""
+        n = fn(self.handle, *args, None)
+        if missing is not None and n < 0:
+            raise abi.HtnError(missing)
+        arr = np.zeros(max(n, 1), dtype=dtype)
+        fn(self.handle, *args, arr.ctypes.data)
+        return arr[:n]
+
+    def _sector_bond(self, rows) -> Bond:
+        return Bond({(int(r["N"]), int(r["j"])): int(r["count"]) for r in rows}, self.sym)
+
     def bond(self, b) -> Bond:
-        n = self.lib.htn_mps_bond(self.handle, b, None)
-        arr = np.zeros(max(n, 1), dtype=abi.SECTOR_DT)
-        self.lib.htn_mps_bond(self.handle, b, arr.ctypes.data)
-        return Bond({(int(r["N"]), int(r["j"])): int(r["count"]) for r in arr[:n]}, self.sym)
+        return self._sector_bond(self._table(self.lib.htn_mps_bond, abi.SECTOR_DT, b))
 
     def bond_dims(self):
         """`dim_state` analogue (src/HubbardFunctions.jl:1399-1405): TensorKit dim of each bond"""
@@ -314,10 +329,13 @@ class DMRG2:
     def bond_of_site(self, i, side):
         key = ("_b", i + side)
         cache = self.__dict__.setdefault("_bond_cache", {})
-        # bonds change with every update: the cache is dropped in update_bond / sweep
+        # bonds change with every update: the cache is dropped by _step / _sweep (and by variance)
         if key not in cache:
             cache[key] = self.bond(i + side)
         return cache[key]
+
+    def _drop_bond_cache(self):
+        self.__dict__.pop("_bond_cache", None)
 
     def site_kind(self, i):
         k = C.c_int32(0)
@@ -326,7 +344,7 @@ class DMRG2:
 
     def env_data(self, side, b):
         """flat environment (library block order) on bond b; side 'L' / 'R'"""
-        sd = 0 if side == "L" else 1
+        sd = _side(side)
         n = self.lib.htn_mps_env_size(self.handle, sd, b)
         if n < 0:
             raise abi.HtnError(f"environment {side} of bond {b} does not exist")
@@ -337,23 +355,15 @@ class DMRG2:
     def env_bond(self, side, b) -> Bond:
         """the bond table the environment on bond b was built on (left: last rightward update of that bond, right: last
         leftward update -- a truncation by dimension may keep different counts in between)"""
-        sd = 0 if side == "L" else 1
-        n = self.lib.htn_mps_env_bond(self.handle, sd, b, None)
-        if n < 0:
-            raise abi.HtnError(f"environment {side} of bond {b} does not exist")
-        arr = np.zeros(max(n, 1), dtype=abi.SECTOR_DT)
-        self.lib.htn_mps_env_bond(self.handle, sd, b, arr.ctypes.data)
-        return Bond({(int(r["N"]), int(r["j"])): int(r["count"]) for r in arr[:n]}, self.sym)
+        return self._sector_bond(self._table(self.lib.htn_mps_env_bond, abi.SECTOR_DT, _side(side), b,
+                                             missing=f"environment {side} of bond {b} does not exist"))
 
     def download_env(self, side, b):
         """{(x, w, y): matrix}: left env keys (bra, w, ket) -> [n_bra, n_ket]; right env (ket, w, bra) -> [n_ket, n_bra]"""
-        sd = 0 if side == "L" else 1
-        nb = self.lib.htn_mps_env_blocks(self.handle, sd, b, None)
-        blk = np.zeros(max(nb, 1), dtype=abi.ENV_BLOCK_DT)
-        self.lib.htn_mps_env_blocks(self.handle, sd, b, blk.ctypes.data)
+        blk = self._table(self.lib.htn_mps_env_blocks, abi.ENV_BLOCK_DT, _side(side), b)
         flat = self.env_data(side, b)
         out = {}
-        for r in blk[:nb]:
+        for r in blk:
             m, n, off = int(r["rows"]), int(r["cols"]), int(r["off"])
             out[((int(r["aN"]), int(r["aj"])), int(r["w"]), (int(r["bN"]), int(r["bj"])))] = \
                 flat[off:off + m * n].reshape(n, m).T.copy()
@@ -367,11 +377,16 @@ class DMRG2:
 
     def apply_heff(self, i, x):
         """y = H_eff(bond i, i+1) x on host vectors in the library's theta layout"""
+        return self._apply_host("htn_heff2_apply", self.lib.htn_heff2_apply, lambda: self.lib.htn_mps_theta_size(self.handle, i), i, x)
+
+    def _apply_host(self, what, fn, size, i, x):
+        """y = fn(i) x, an effective Hamiltonian of the library applied to a host vector: upload, one call, download.  size():
+        the elements the library expects (queried after x is converted; it may raise)"""
         x = np.ascontiguousarray(x, dtype=np.complex128)
-        n = self.lib.htn_mps_theta_size(self.handle, i)
+        n = size()
         assert x.shape == (n,)
         y = np.zeros(n, dtype=np.complex128)
-        self._check(self.lib.htn_heff2_apply(self.handle, i, x.ctypes.data, y.ctypes.data), "htn_heff2_apply")
+        self._check(fn(self.handle, i, x.ctypes.data, y.ctypes.data), what)
         return y
 
     def centre_energy(self):
@@ -417,30 +432,44 @@ class DMRG2:
         return h.value, m.value
 
     # ---- updates ----------------------------------------------------------------------------------
-    def update_bond(self, i, direction, placement, optimise=True, record=True, cutoff=None):
-        """optimise sites (i, i+1); placement 'right': A_i = U, centre S V^H on i+1 (+ left env); 'left': centre U S on
-        i, B_{i+1} = V^H (+ right env).  optimise=False only moves the centre (E = <theta|H|theta>)."""
-        self.__dict__.pop("_bond_cache", None)
+    def _step(self, what, call, record, cutoff=None, drop_cache=True, sets_energy=True) -> BondStats:
+        """one single-update entry of the library, call(opts, stats) -> status, with its one record.  The updates differ in
+        three things, which their wrappers state: whether the bond tables may change (drop_cache: the cache of bond_of_site goes
+        before the call), whether a recorded update's `energy` is an energy of the state (sets_energy: it becomes self.energy),
+        and what they return (the BondStats returned here, or its energy)."""
+        if drop_cache:
+            self._drop_bond_cache()
         st = np.zeros(1, dtype=abi.BOND_STATS_DT)
         o = self._opts(cutoff)
-        self._check(self.lib.htn_bond_update(self.handle, i, direction, 0 if placement == "right" else 1,
-                                             1 if optimise else 0, C.byref(o), st.ctypes.data), "htn_bond_update")
+        self._check(call(C.byref(o), st.ctypes.data), what)
         s = _stats(st[0])
         if record:
             self.stats.append(s)
-            self.energy = s.energy
-        return s.energy
+            if sets_energy:
+                self.energy = s.energy
+        return s
+
+    def _sweep(self, what, n, call, sets):
+        """one sweep entry of the library, call(opts, stats, *scalars) -> status, with its n records, which go to `stats`.
+        sets: the attributes that take the call's scalar outputs (doubles), in the order of its arguments."""
+        self._drop_bond_cache()
+        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
+        out = [C.c_double(0.0) for _ in sets]
+        o = self._opts()
+        self._check(call(C.byref(o), st.ctypes.data, *[C.byref(v) for v in out]), what)
+        self.stats.extend(_stats(r) for r in st)
+        for name, v in zip(sets, out):
+            setattr(self, name, v.value)
+
+    def update_bond(self, i, direction, placement, optimise=True, record=True, cutoff=None):
+        """optimise sites (i, i+1); placement 'right': A_i = U, centre S V^H on i+1 (+ left env); 'left': centre U S on
+        i, B_{i+1} = V^H (+ right env).  optimise=False only moves the centre (E = <theta|H|theta>)."""
+        return self._step("htn_bond_update", lambda o, st: self.lib.htn_bond_update(
+            self.handle, i, direction, 0 if placement == "right" else 1, 1 if optimise else 0, o, st), record, cutoff).energy
 
     def sweep(self):
         """one sweep in MPSKit's DMRG2 order (bonds 0..L-2 rightwards, L-3..0 leftwards), one library call"""
-        self.__dict__.pop("_bond_cache", None)
-        n = 2 * self.L - 3
-        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
-        E = C.c_double(0.0)
-        o = self._opts()
-        self._check(self.lib.htn_dmrg2_sweep(self.handle, C.byref(o), st.ctypes.data, C.byref(E)), "htn_dmrg2_sweep")
-        self.stats.extend(_stats(r) for r in st)
-        self.energy = E.value
+        self._sweep("htn_dmrg2_sweep", 2 * self.L - 3, lambda o, st, E: self.lib.htn_dmrg2_sweep(self.handle, o, st, E), ("energy",))
         return self.energy
 
     # ---- one-site DMRG at fixed bond tables (htn_site_update / htn_dmrg1_sweep) --------------------
@@ -453,29 +482,14 @@ class DMRG2:
         (optimise=False: <x|H_eff|x> only), then direction +1: QR, site i becomes a left isometry, the centre moves to
         i + 1; -1: LQ, the centre moves to i - 1; 0: it stays.  Bond tables never change.  Returns the eigenvalue, which
         is <psi|H|psi> of the stored state (nothing is truncated)."""
-        self.__dict__.pop("_bond_cache", None)
-        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
-        o = self._opts()
-        self._check(self.lib.htn_site_update(self.handle, i, direction, 1 if optimise else 0, C.byref(o), st.ctypes.data),
-                    "htn_site_update")
-        s = _stats(st[0])
-        if record:
-            self.stats.append(s)
-            self.energy = s.energy
-        return s.energy
+        return self._step("htn_site_update", lambda o, st: self.lib.htn_site_update(
+            self.handle, i, direction, 1 if optimise else 0, o, st), record).energy
 
     def sweep1(self):
         """one one-site sweep at the current bond tables (sites 0..L-2 rightwards, L-1..1 leftwards, 2L-2 updates, one
         library call); the centre ends on site 0.  Grow the bonds with sweep() first.  The Schmidt spectra
         (`spectrum`) keep the values of the last two-site update of each bond."""
-        self.__dict__.pop("_bond_cache", None)
-        n = 2 * self.L - 2
-        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
-        E = C.c_double(0.0)
-        o = self._opts()
-        self._check(self.lib.htn_dmrg1_sweep(self.handle, C.byref(o), st.ctypes.data, C.byref(E)), "htn_dmrg1_sweep")
-        self.stats.extend(_stats(r) for r in st)
-        self.energy = E.value
+        self._sweep("htn_dmrg1_sweep", 2 * self.L - 2, lambda o, st, E: self.lib.htn_dmrg1_sweep(self.handle, o, st, E), ("energy",))
         return self.energy
 
     # ---- time evolution: two-site TDVP (htn_bond_evolve / htn_site_evolve / htn_tdvp2_sweep / htn_mps_set_mpo) ----
@@ -483,26 +497,16 @@ class DMRG2:
         """theta <- exp(-i dt H_eff) theta on sites (i, i+1), then SVD, truncation, write-back and environment move as
         update_bond; dt complex (-i beta: imaginary time).  -> BondStats (energy = <theta|H_eff|theta> before the step,
         residual = the error estimate of the exponential)"""
-        self.__dict__.pop("_bond_cache", None)
-        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
-        o, dt = self._opts(), complex(dt)
-        self._check(self.lib.htn_bond_evolve(self.handle, i, direction, 0 if placement == "right" else 1, dt.real, dt.imag,
-                                             C.byref(o), st.ctypes.data), "htn_bond_evolve")
-        s = _stats(st[0])
-        if record:
-            self.stats.append(s)
-            self.energy = s.energy
-        return s
+        dt = complex(dt)
+        return self._step("htn_bond_evolve", lambda o, st: self.lib.htn_bond_evolve(
+            self.handle, i, direction, 0 if placement == "right" else 1, dt.real, dt.imag, o, st), record)
 
     def evolve_site(self, i, dt, record=True):
-        """centre on site i <- exp(-i dt H_eff1) centre in place (no gauge move); -> BondStats"""
-        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
-        o, dt = self._opts(), complex(dt)
-        self._check(self.lib.htn_site_evolve(self.handle, i, dt.real, dt.imag, C.byref(o), st.ctypes.data), "htn_site_evolve")
-        s = _stats(st[0])
-        if record:
-            self.stats.append(s)
-        return s
+        """centre on site i <- exp(-i dt H_eff1) centre in place (no gauge move); -> BondStats.  No bond table changes (the
+        cache of bond_of_site stays) and the record's energy does not become self.energy."""
+        dt = complex(dt)
+        return self._step("htn_site_evolve", lambda o, st: self.lib.htn_site_evolve(self.handle, i, dt.real, dt.imag, o, st), record,
+                          drop_cache=False, sets_energy=False)
 
     def tdvp_sweep(self, dt):
         """one symmetric two-site TDVP step of length dt (complex; -i beta: imaginary time), one library call: half steps on
@@ -510,16 +514,9 @@ class DMRG2:
         ends on site 0, the state stays normalised; `log_norm` holds the logarithm of the norm change the exponentials produced
         (0 for real dt), `trunc_weights` the discarded weight per record.  lanczos_tol is the tolerance of the exponential.
         Returns <psi|H|psi> as the last bond step saw it."""
-        self.__dict__.pop("_bond_cache", None)
-        n = 2 * self.L - 2
-        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
-        E, lg = C.c_double(0.0), C.c_double(0.0)
-        o, dt = self._opts(), complex(dt)
-        self._check(self.lib.htn_tdvp2_sweep(self.handle, dt.real, dt.imag, C.byref(o), st.ctypes.data, C.byref(E), C.byref(lg)),
-                    "htn_tdvp2_sweep")
-        self.stats.extend(_stats(r) for r in st)
-        self.energy = E.value
-        self.log_norm = lg.value
+        dt = complex(dt)
+        self._sweep("htn_tdvp2_sweep", 2 * self.L - 2, lambda o, st, E, lg: self.lib.htn_tdvp2_sweep(
+            self.handle, dt.real, dt.imag, o, st, E, lg), ("energy", "log_norm"))
         return self.energy
 
     # ---- time evolution at fixed bond tables: one-site TDVP (htn_site_evolve_move / htn_tdvp1_sweep / htn_heff0_apply) ----
@@ -527,16 +524,9 @@ class DMRG2:
         """one move of one-site TDVP (the centre must be on site i): site <- exp(-i dt_fwd H_eff1) site, QR (direction +1) or
         LQ (-1) as update_site, the triangular factor C <- exp(-i dt_back H_eff0) C on the bond crossed, C into the neighbour,
         which becomes the centre.  Bond tables never change.  -> BondStats (energy = <psi|H|psi> before the move)"""
-        self.__dict__.pop("_bond_cache", None)
-        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
-        o, f, b = self._opts(), complex(dt_fwd), complex(dt_back)
-        self._check(self.lib.htn_site_evolve_move(self.handle, i, direction, f.real, f.imag, b.real, b.imag, C.byref(o),
-                                                  st.ctypes.data), "htn_site_evolve_move")
-        s = _stats(st[0])
-        if record:
-            self.stats.append(s)
-            self.energy = s.energy
-        return s
+        f, b = complex(dt_fwd), complex(dt_back)
+        return self._step("htn_site_evolve_move", lambda o, st: self.lib.htn_site_evolve_move(
+            self.handle, i, direction, f.real, f.imag, b.real, b.imag, o, st), record)
 
     def tdvp1_sweep(self, dt):
         """one symmetric one-site TDVP step of length dt (complex; -i beta: imaginary time) at the current bond tables, one
@@ -545,16 +535,9 @@ class DMRG2:
         normalised and `log_norm` holds the logarithm of the norm change (0 for real dt).  Grow the bonds with sweep() or
         tdvp_sweep() first; the Schmidt spectra (`spectrum`) keep the values of the last two-site update of each bond.
         Returns <psi|H|psi> as the closing step on site 0 saw it."""
-        self.__dict__.pop("_bond_cache", None)
-        n = 2 * self.L - 2
-        st = np.zeros(n, dtype=abi.BOND_STATS_DT)
-        E, lg = C.c_double(0.0), C.c_double(0.0)
-        o, dt = self._opts(), complex(dt)
-        self._check(self.lib.htn_tdvp1_sweep(self.handle, dt.real, dt.imag, C.byref(o), st.ctypes.data, C.byref(E), C.byref(lg)),
-                    "htn_tdvp1_sweep")
-        self.stats.extend(_stats(r) for r in st)
-        self.energy = E.value
-        self.log_norm = lg.value
+        dt = complex(dt)
+        self._sweep("htn_tdvp1_sweep", 2 * self.L - 2, lambda o, st, E, lg: self.lib.htn_tdvp1_sweep(
+            self.handle, dt.real, dt.imag, o, st, E, lg), ("energy", "log_norm"))
         return self.energy
 
     # ---- correction-vector sweeps (htn_bond_solve / htn_cv_sweep) ------------------------------------------------
@@ -573,15 +556,11 @@ class DMRG2:
         amplitude, started from the current theta; then SVD, truncation, write-back and environment move as update_bond.
         lanczos_tol is the tolerance of the solve.  -> (BondStats with energy = Im <p|theta_new> and residual = the relative
         residual of the solve, <p|theta_new> = <b|x> before truncation, amplitude)"""
-        self.__dict__.pop("_bond_cache", None)
-        st = np.zeros(1, dtype=abi.BOND_STATS_DT)
-        o, z = self._opts(), complex(z)
+        z = complex(z)
         amp, bx = C.c_double(0.0), (C.c_double * 2)()
-        self._check(self.lib.htn_bond_solve(self.handle, i, direction, 0 if placement == "right" else 1, z.real, z.imag, C.byref(o),
-                                            st.ctypes.data, C.byref(amp), bx), "htn_bond_solve")
-        s = _stats(st[0])
-        if record:
-            self.stats.append(s)
+        s = self._step("htn_bond_solve", lambda o, st: self.lib.htn_bond_solve(
+            self.handle, i, direction, 0 if placement == "right" else 1, z.real, z.imag, o, st, C.byref(amp), bx), record,
+            sets_energy=False)              # (the record's energy is Im <p|theta_new>, no energy of the state)
         self._amplitude = amp.value
         return s, complex(bx[0], bx[1]), amp.value
 
@@ -589,14 +568,10 @@ class DMRG2:
         """one correction-vector sweep for (z - H) x = b, one library call: bonds 0..L-2 rightwards, L-2..0 leftwards (2L-2
         records); the centre starts and ends on site 0.  -> (<b|x> of the last bond before its truncation, amplitude): the state
         is amplitude x (the normalised stored tensors)."""
-        self.__dict__.pop("_bond_cache", None)
-        st = np.zeros(2 * self.L - 2, dtype=abi.BOND_STATS_DT)
-        o, z = self._opts(), complex(z)
-        amp, bx = C.c_double(0.0), (C.c_double * 2)()
-        self._check(self.lib.htn_cv_sweep(self.handle, z.real, z.imag, C.byref(o), st.ctypes.data, C.byref(amp), bx), "htn_cv_sweep")
-        self.stats.extend(_stats(r) for r in st)
-        self._amplitude = amp.value
-        return complex(bx[0], bx[1]), amp.value
+        z, bx = complex(z), (C.c_double * 2)()
+        self._sweep("htn_cv_sweep", 2 * self.L - 2, lambda o, st, amp: self.lib.htn_cv_sweep(
+            self.handle, z.real, z.imag, o, st, amp, bx), ("_amplitude",))       # (energy stays: a solve has none)
+        return complex(bx[0], bx[1]), self._amplitude
 
     def bond_size(self, b) -> int:
         """elements of a vector in bond layout on bond b: one n_c x n_c column-major matrix per sector, in the order of
@@ -609,12 +584,7 @@ class DMRG2:
     def apply_heff0(self, b, x):
         """y = H_eff0(bond b) x on host vectors in bond layout (bond_size(b)); the centre must be on site b - 1 or b with both
         environments of the bond present, as after a gauge move across it"""
-        x = np.ascontiguousarray(x, dtype=np.complex128)
-        n = self.bond_size(b)
-        assert x.shape == (n,)
-        y = np.zeros(n, dtype=np.complex128)
-        self._check(self.lib.htn_heff0_apply(self.handle, b, x.ctypes.data, y.ctypes.data), "htn_heff0_apply")
-        return y
+        return self._apply_host("htn_heff0_apply", self.lib.htn_heff0_apply, lambda: self.bond_size(b), b, x)
 
     def set_mpo(self, mpo):
         """swap the Hamiltonian under the state (a quench): same symmetry, chain length and site multiplets, centre on site
@@ -637,12 +607,7 @@ class DMRG2:
     def apply_heff1(self, i, x):
         """y = H_eff(site i) x on host vectors in the stored layout of site i (the flat vector of `download_site`'s
         blocks: htn_mps_get_site); the centre must be on site i"""
-        x = np.ascontiguousarray(x, dtype=np.complex128)
-        n = self.lib.htn_mps_site_theta_size(self.handle, i)
-        assert x.shape == (n,)
-        y = np.zeros(n, dtype=np.complex128)
-        self._check(self.lib.htn_heff1_apply(self.handle, i, x.ctypes.data, y.ctypes.data), "htn_heff1_apply")
-        return y
+        return self._apply_host("htn_heff1_apply", self.lib.htn_heff1_apply, lambda: self.lib.htn_mps_site_theta_size(self.handle, i), i, x)
 
     def site_vector(self, i):
         """the stored data of site i as one flat vector (the Lanczos vector of a one-site update when i is the centre)"""
@@ -898,7 +863,7 @@ class DMRG2:
         anywhere and is back where it was afterwards, the state is the same state (to rounding), `energy` and `stats` are left
         alone.  An applied state reports the variance of the normalised state.  timed=True also fills .split = seconds spent in
         (theta + applies, projections, moves), each closed by a stream sync."""
-        self.__dict__.pop("_bond_cache", None)
+        self._drop_bond_cache()
         site, bond = np.zeros(self.L), np.zeros(max(self.L - 1, 1))
         E, split = C.c_double(0.0), np.zeros(3)
         self._check(self.lib.htn_mps_variance(self.handle, site.ctypes.data, bond.ctypes.data, C.byref(E),
